@@ -8,7 +8,11 @@ One "step" = one batch of fits: T trials x 6 output GPs (vwindices of P2noise.jl
 each GP with its own theta (config.json P2_MAX2048 jittered, as during optimisation), inputs
 resident in HBM before the timed region.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N>1 the ranks run one per GPU over
+Launch: python bench.py [--gpus N --steps K --warmup W].  A plain run sets up, warms up, times the K
+steps and prints the result line (and with --dump-outputs DIR writes the last timed step's results
+as DIR/<name>.npy).  --full adds the legs that take runs of their own: the per-kernel roofline
+pass, the optimiser leg, the CPU baseline and the accuracy check against the oracle (each of them
+can be left out with --no-prof / --no-opt / --no-cpu).  For N>1 the ranks run one per GPU over
 RCCL: under torch.distributed.run (the driver's form), or started by this script itself as a
 torch.distributed.run child when WORLD_SIZE is unset; fewer visible GPUs than N is an error
 (--rehearse lets ranks share devices with a gloo control plane, for rehearsals only), and every
@@ -313,6 +317,17 @@ def _progress(rank: int, msg: str):
         print(f"bench: {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(dirname: str, r: dict, rank: int):
+    """The results of the last timed step, as rb.evaluate returned them ((local trial, output, ...)
+    arrays: mll, grad, mu, var, status, info), one float64 DIR/<name>.npy each (~0.5 MB in all at
+    the default size).  Rank 0 writes <name>.npy, rank k > 0 writes <name>_rank<k>.npy."""
+    out = pathlib.Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for k, v in r.items():
+        np.save(out / f"{k}{sfx}.npy", np.ascontiguousarray(v, dtype=np.float64))
+
+
 def _launch_ranks(args) -> int:
     """`bench.py --gpus N` (N > 1) started without a launcher: start N ranks, one per GPU, as a
     torch.distributed.run child (the driver's own command line), and return its exit code.  Runs
@@ -344,9 +359,14 @@ def main():
     # measured 5578 fits/s against 5489 at 32 trials and 5551 at 42 (scratch/bsweep.sh, one box)
     ap.add_argument("--trials", type=int, default=int(os.environ.get("GPRX_BENCH_TRIALS", "40")),
                     help="P2 trials per GPU per step (x6 output GPs)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-prof", action="store_true")
-    ap.add_argument("--no-opt", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel roofline pass, the optimiser leg and "
+                         "the CPU baseline / accuracy leg (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline / accuracy leg")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: leave out the per-kernel timing pass")
+    ap.add_argument("--no-opt", action="store_true", help="with --full: leave out the optimiser leg")
     ap.add_argument("--opt-evals", type=int, default=30)
     ap.add_argument("--rehearse", action="store_true",
                     help="allow more ranks than visible GPUs (ranks share devices, gloo control plane): a "
@@ -411,6 +431,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     ok = ok and bool(np.all(r["status"] == 0))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, rank)
     r = {k: np.asarray(v).reshape((B,) + np.asarray(v).shape[2:]) for k, v in r.items()}  # per slot
     per_rank = [B * args.steps / dt]
     if dist is not None:
@@ -428,7 +450,7 @@ def main():
     # roofline: per-kernel HIP-event timing on the library stream, same workload, separate pass
     roof = parts = None
     kern = {}
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         _progress(rank, "per-kernel timing pass")
         ctx.set_profiling(True)
         ctx.reset_stats()
@@ -461,7 +483,7 @@ def main():
     # optimize!'s closing refit) is the figure; the host lock-step restatement
     # (gprx.optim.optimize_batch) is timed beside it and must give bit-identical minimisers.
     opt = None
-    if not args.no_opt:
+    if args.full and not args.no_opt:
         from gprx.optim import LBFGS, Options, compare_optimisers, optimize_batch
 
         def timed(fn):
@@ -494,7 +516,7 @@ def main():
                "device_vs_host": cmp,
                "stopped_by": {k: sum(1 for r in res if r.stopped_by == k) for k in sorted({r.stopped_by for r in res})}}
     cpu = acc = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         _progress(rank, "CPU baseline leg")
         if world == 1:  # the CPU baseline is an N=1 figure
             cpu, acc = cpu_baseline(X, Y, T, XT, gpu=r)
