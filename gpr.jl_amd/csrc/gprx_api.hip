@@ -252,10 +252,7 @@ void factor_rec(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, i
           [&] { gprx::launch_leaf(db, o, n, upd, st); }, n);
     return;
   }
-#ifndef GPRX_NODE8
-#define GPRX_NODE8 1
-#endif
-  if (GPRX_NODE8 && n == 8 && leaf == 4 && db.B >= 32) {  // the whole node in one launch (k_node8)
+  if (n == 8 && leaf == 4 && db.B >= 32) {  // the whole node in one launch (k_node8)
     const double m = 4 * T;
     // the 4-wave form (two slots per CU, bit-identical) on request only: measured slower at every
     // batch size ("Two slots per CU"): a paired slot's fp64 VALU chain and MFMAs share

@@ -132,7 +132,8 @@ def _load():
 
 # the library's sources, in the order gpr.jl_amd/Makefile hashes them (SRC then HDR)
 BUILD_SOURCES = ["csrc/gprx_kernels.hip", "csrc/gprx_lbfgs.hip", "csrc/gprx_projection.hip", "csrc/gprx_api.hip",
-                 "csrc/gprx_internal.h", "../include/gprx.h"]
+                 "csrc/gprx_internal.h", "csrc/gprx_device.h", "csrc/gprx_cores.h", "csrc/gprx_stamps.h",
+                 "csrc/gprx_gemm.h", "csrc/gprx_factor.h", "../include/gprx.h"]
 
 
 def source_build_id():

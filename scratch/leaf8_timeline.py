@@ -1,5 +1,6 @@
 """Timeline of the overlapped leaf (k_leaf8) on the bench workload, from a diagnostic build's
-stamps (scratch/devbuild.sh l8stamps -DGPRX_STAMPS -DGPRX_NODE8=0 -DGPRX_LAUUM_FWD -DGPRX_SLOTWG_N=0):
+stamps (scratch/devbuild.sh l8stamps -DGPRX_STAMPS -DGPRX_LAUUM_FWD -DGPRX_SLOTWG_N=0; the leaf as a
+launch of its own at n = 8 needs a tree up to commit 05bc94e, whose switch for it has since gone):
 
     GPRX_LIB=scratch/var/libgprx_l8stamps.so python scratch/leaf8_timeline.py [trials]
 
