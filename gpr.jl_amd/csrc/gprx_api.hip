@@ -71,6 +71,17 @@ struct gprx_batch {
   int* opt_active = nullptr;  // device, B: the optimiser's per-round evaluation mask (DevBatch::active)
   double* opt_trace = nullptr;  // caller's host buffer for gprx_batch_set_opt_trace (diagnostics)
   int opt_trace_rounds = 0;
+  // joint-covariance workspace (gprx_batch_predict_cov / gprx_batch_sample), allocated on first use
+  // for the batch's current Mpad and re-allocated when gprx_batch_set_test grows it
+  double* cov_vt = nullptr;   // B x [Npad][Mpad]  V^T
+  double* cov_sig = nullptr;  // B x Mpad^2        Sigma, compact [M][M] per slot
+  double* cov_f = nullptr;    // B x Mpad^2        its factor
+  double* cov_z = nullptr;    // B x Mpad^2        Z, up to Mpad vectors per slot a pass
+  double* cov_smp = nullptr;  // B x Mpad^2        samples of the pass
+  double* cov_jit = nullptr;  // B
+  int* cov_st = nullptr;      // B
+  double* h_cov = nullptr;    // pinned, B doubles + B ints: jitter and status
+  int cov_mpad = 0;           // the Mpad the workspace was sized for (0: none)
   bool factored = false;
   bool have_train = false;
   bool have_test = false;
@@ -599,6 +610,7 @@ static void batch_free(gprx_batch* b) {
   if (b->h_mu) (void)hipHostFree(b->h_mu);
   if (b->h_var) (void)hipHostFree(b->h_var);
   if (b->h_status) (void)hipHostFree(b->h_status);
+  if (b->h_cov) (void)hipHostFree(b->h_cov);
   delete b;
 }
 
@@ -806,6 +818,152 @@ int gprx_batch_predict(gprx_batch* b, double* mu, double* var) {
   std::lock_guard<std::mutex> g(b->ctx->mu);
   if (hipSetDevice(b->ctx->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   return batch_predict_locked(b, mu, var);
+}
+
+// ---- joint predictive covariance and posterior samples (gprx_predcov.h) -------------------------
+// Device bytes of the joint-covariance workspace (cov_alloc): V^T, Sigma, its factor; the Z and
+// sample buffers of a pass and the per-slot jitter and status (the staging term)
+static size_t cov_bytes(size_t B, size_t Npad, size_t Mpad) {
+  return sizeof(double) * B * (Npad * Mpad + 2 * Mpad * Mpad) + sizeof(double) * B * 2 * Mpad * Mpad + B * (sizeof(double) + sizeof(int));
+}
+static bool cov_addressable(size_t Mpad) { return Mpad * Mpad * sizeof(double) < BUF_LIMIT; }
+
+static void cov_free(gprx_batch* b) {
+  void* ps[] = {b->cov_vt, b->cov_sig, b->cov_f, b->cov_z, b->cov_smp, b->cov_jit, b->cov_st};
+  for (void* p : ps)
+    if (p) release_ptr(b, p);
+  b->cov_vt = b->cov_sig = b->cov_f = b->cov_z = b->cov_smp = b->cov_jit = nullptr;
+  b->cov_st = nullptr;
+  if (b->h_cov) (void)hipHostFree(b->h_cov);
+  b->h_cov = nullptr;
+  b->cov_mpad = 0;
+}
+// The workspace for the batch's current Mpad; a failure frees what it got and leaves the batch as
+// it was before the call.
+static int cov_alloc(gprx_batch* b) {
+  gprx_ctx* c = b->ctx;
+  const DevBatch& db = b->db;
+  if (b->cov_mpad == db.Mpad) return GPRX_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  cov_free(b);
+  const size_t B = db.B, mm = (size_t)db.Mpad * db.Mpad;
+  int rc;
+  if ((rc = dalloc(b, &b->cov_vt, B * db.Npad * db.Mpad)) || (rc = dalloc(b, &b->cov_sig, B * mm)) ||
+      (rc = dalloc(b, &b->cov_f, B * mm)) || (rc = dalloc(b, &b->cov_z, B * mm)) || (rc = dalloc(b, &b->cov_smp, B * mm)) ||
+      (rc = dalloc(b, &b->cov_jit, B)) || (rc = dalloc(b, &b->cov_st, B))) {
+    cov_free(b);
+    return rc;
+  }
+  if (hipHostMalloc((void**)&b->h_cov, B * (sizeof(double) + sizeof(int))) != hipSuccess) {
+    (void)hipGetLastError();
+    b->h_cov = nullptr;
+    cov_free(b);
+    return set_err(c, GPRX_OUT_OF_MEMORY, "hipHostMalloc failed");
+  }
+  b->cov_mpad = db.Mpad;
+  return GPRX_OK;
+}
+
+// mu (copied to the caller when non-NULL) and Sigma on the device, from the last factorisation:
+// the prediction's own cross-covariance and mean launches, then pred_whiten and pred_cov
+static int cov_compute(gprx_batch* b, double* mu) {
+  gprx_ctx* c = b->ctx;
+  DevBatch& db = b->db;
+  if (!b->factored) return set_err(c, GPRX_NOT_READY, "joint covariance before a successful factorisation");
+  if (!b->have_test || db.M == 0) return set_err(c, GPRX_NOT_READY, "joint covariance without test points (gprx_batch_set_test)");
+  if (!cov_addressable(db.Mpad))
+    return set_err(c, GPRX_INVALID_ARGUMENT, "joint covariance: Mpad^2 * 8 exceeds the 2 GiB buffer range");
+  int rc = cov_alloc(b);
+  if (rc) return rc;
+  if ((rc = batch_predict_locked(b, mu, nullptr))) return rc;
+  const double N = db.N, M = db.M, B = db.B;
+  timed(c, c->stream, "pred_whiten", B * N * N * M, B * 8.0 * (N * N / 2 + 2.0 * N * db.Mpad),
+        [&] { gprx::launch_pred_whiten(db, b->cov_vt, c->stream); });
+  timed(c, c->stream, "pred_cov", B * N * M * M, B * 8.0 * (N * db.Mpad + M * M + 2.0 * M * db.d),
+        [&] { gprx::launch_pred_cov(db, b->cov_vt, b->cov_sig, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  return GPRX_OK;
+}
+static void nan_fill(double* p, size_t n) {
+  for (size_t i = 0; i < n; ++i) p[i] = NAN;
+}
+
+int gprx_batch_cov_bytes(int B, int N, int M_max, uint64_t* bytes) {
+  if (bytes) *bytes = 0;
+  if (!bytes || B < 1 || N < 1 || M_max < 0) return GPRX_INVALID_ARGUMENT;
+  const size_t Npad = pad64(N), Mpad = std::max<size_t>(pad64(M_max), TS);
+  if (!sizes_addressable(Npad, Mpad) || !cov_addressable(Mpad)) return GPRX_INVALID_ARGUMENT;
+  *bytes = cov_bytes((size_t)B, Npad, Mpad);
+  return GPRX_OK;
+}
+
+int gprx_batch_predict_cov(gprx_batch* b, double* mu, double* cov) {
+  if (!b || !cov) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  int rc = cov_compute(b, mu);
+  if (rc) return rc;
+  const DevBatch& db = b->db;
+  const size_t M = db.M;
+  // Sigma is compact on the device ([M][M] per slot, slots M M apart): one copy
+  HIPCHK(c, hipMemcpyAsync(cov, b->cov_sig, (size_t)db.B * M * M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  for (int s = 0; s < db.B; ++s)  // h_status: the evaluation that factorised the batch (gprx_batch_alpha)
+    if (b->h_status[s] != GPRX_OK) {
+      nan_fill(cov + (size_t)s * M * M, M * M);
+      if (mu) nan_fill(mu + (size_t)s * M, M);
+    }
+  return GPRX_OK;
+}
+
+int gprx_batch_sample(gprx_batch* b, const double* Z, int S, int64_t zss, double* samples, double* jitter, int* status) {
+  if (!b || !Z || !samples || S < 1 || zss < 0) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const DevBatch& db = b->db;
+  if (b->factored && b->have_test && db.M > 1024)
+    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_sample: M > 1024 test points");
+  int rc = cov_compute(b, nullptr);
+  if (rc) return rc;
+  const size_t M = db.M, B = db.B, mm = (size_t)db.Mpad * db.Mpad;
+  timed(c, c->stream, "cov_chol", (double)B * M * M * M / 3.0, (double)B * 8.0 * 2.0 * M * M,
+        [&] { gprx::launch_cov_chol(db, b->cov_sig, b->cov_f, mm, b->cov_jit, b->cov_st, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  // Z and the samples pass through device buffers of Mpad vectors per slot: S beyond that in passes
+  for (int s0 = 0; s0 < S; s0 += db.Mpad) {
+    const size_t sc = std::min<size_t>(db.Mpad, S - s0), w = sc * M * sizeof(double);
+    if (zss == 0)
+      HIPCHK(c, hipMemcpyAsync(b->cov_z, Z + (size_t)s0 * M, w, hipMemcpyHostToDevice, c->stream));
+    else
+      HIPCHK(c, hipMemcpy2DAsync(b->cov_z, mm * sizeof(double), Z + (size_t)s0 * M, (size_t)zss * sizeof(double), w, B,
+                                 hipMemcpyHostToDevice, c->stream));
+    timed(c, c->stream, "cov_sample", (double)B * sc * M * M, (double)B * 8.0 * (M * M / 2.0 + 2.0 * sc * M), [&] {
+      gprx::launch_cov_sample(db, b->cov_f, mm, b->cov_z, zss == 0 ? 0 : mm, b->cov_smp, mm, (int)sc, b->cov_st, c->stream);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy2DAsync(samples + (size_t)s0 * M, (size_t)S * M * sizeof(double), b->cov_smp, mm * sizeof(double), w, B,
+                               hipMemcpyDeviceToHost, c->stream));
+  }
+  double* hj = b->h_cov;
+  int* hs = (int*)(b->h_cov + B);
+  HIPCHK(c, hipMemcpyAsync(hj, b->cov_jit, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hs, b->cov_st, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  int first = GPRX_OK;
+  for (size_t s = 0; s < B; ++s) {
+    // a slot whose evaluation failed: NaN rows (the kernels wrote them), not a failure of this call
+    const bool dead = b->h_status[s] != GPRX_OK;
+    if (dead) nan_fill(samples + s * S * M, (size_t)S * M);
+    if (jitter) jitter[s] = dead ? NAN : hj[s];
+    if (status) status[s] = dead ? b->h_status[s] : hs[s];
+    if (!dead && hs[s] != GPRX_OK && first == GPRX_OK) first = hs[s];
+  }
+  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_sample: ") + gprx_status_string(first));
+  return first;
 }
 
 // ---- device hyper-parameter optimisation (gprx_lbfgs.hip) ---------------------------------------
@@ -1053,6 +1211,20 @@ int gprx_gp_predict(gprx_gp* gp, const double* Xs, int M, double* mu, double* va
   int rc = gprx_batch_set_test(gp->batch, Xs, M, 0, GPRX_MEM_HOST);
   if (rc) return rc;
   return gprx_batch_predict(gp->batch, mu, var);
+}
+
+int gprx_gp_predict_cov(gprx_gp* gp, const double* Xs, int M, double* mu, double* cov) {
+  if (!gp || !Xs || M < 1 || !cov) return GPRX_INVALID_ARGUMENT;
+  int rc = gprx_batch_set_test(gp->batch, Xs, M, 0, GPRX_MEM_HOST);
+  if (rc) return rc;
+  return gprx_batch_predict_cov(gp->batch, mu, cov);
+}
+
+int gprx_gp_sample(gprx_gp* gp, const double* Xs, int M, const double* Z, int S, double* samples, double* jitter) {
+  if (!gp || !Xs || M < 1 || !Z || !samples || S < 1) return GPRX_INVALID_ARGUMENT;
+  int rc = gprx_batch_set_test(gp->batch, Xs, M, 0, GPRX_MEM_HOST);
+  if (rc) return rc;
+  return gprx_batch_sample(gp->batch, Z, S, 0, samples, jitter, nullptr);
 }
 
 // ---- rollout in minimal coordinates ------------------------------------------------------------

@@ -245,6 +245,14 @@ void launch_finalize(const DevBatch& b, int want_grad, hipStream_t s);
 void launch_pred_cross(const DevBatch& b, hipStream_t s);
 void launch_pred_final(const DevBatch& b, hipStream_t s);
 void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s);
+// joint predictive covariance and samples (gprx_predcov.h).  VT: B x [Npad][Mpad] (K*^T's layout);
+// Sig: B x [M][M] compact; F: the factor, ld = M, slot stride fs doubles; Z / smp: [S][M] per slot
+// at strides zs (0 = shared) / ss; jit[B], st[B] as k_cov_chol writes them
+void launch_pred_whiten(const DevBatch& b, double* VT, hipStream_t s);
+void launch_pred_cov(const DevBatch& b, const double* VT, double* Sig, hipStream_t s);
+void launch_cov_chol(const DevBatch& b, const double* Sig, double* F, size_t fs, double* jit, int* st, hipStream_t s);
+void launch_cov_sample(const DevBatch& b, const double* F, size_t fs, const double* Z, size_t zs, double* smp, size_t ss,
+                       int S, const int* st, hipStream_t s);
 void launch_lbfgs(const LbArgs& a, const DevBatch& db, int init, hipStream_t s);  // gprx_lbfgs.hip
 void launch_lbfgs_final(const LbArgs& a, const DevBatch& db, hipStream_t s);
 

@@ -1074,6 +1074,7 @@ static size_t cross_lds(int d) { return (size_t)(2 * d * CS + 2 * DMAX + 4 + 4 *
 // Dynamic-LDS limits above the 64 KB default, for the current device.  Called once per device by
 // gprx_ctx_create (std::call_once per device index) before any launch, so concurrent contexts on
 // other threads never launch a kernel whose attribute is not yet set.
+static void set_predcov_attributes();  // gprx_predcov.h
 void set_kernel_attributes() {
   for (const void* f : {(const void*)k_gram<0>, (const void*)k_gram<1>})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds(DMAX));
@@ -1086,6 +1087,7 @@ void set_kernel_attributes() {
   for (const void* f : {(const void*)k_gemm<REV_A>, (const void*)k_gemm<REV_B>, (const void*)k_gemm<TRI_A_FIRST>})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)linv21_lds_bytes());
   set_lbfgs_attributes();
+  set_predcov_attributes();
 }
 
 void launch_gram(const DevBatch& b, hipStream_t s) {
@@ -1154,3 +1156,6 @@ void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s) {
 }
 
 }  // namespace gprx
+
+// Last: the joint-covariance kernels follow every evaluation kernel in the code object.
+#include "gprx_predcov.h"

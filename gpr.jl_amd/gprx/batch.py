@@ -272,6 +272,38 @@ class GPBatch:
         L.check(L.lib.gprx_batch_predict(self.h, L.dptr(mu), L.dptr(var)), self.ctx.h)
         return mu, var
 
+    def predict_cov(self):
+        """Joint f-space posterior at the current test points from the last run's factorisation
+        [ext predict_f(gp, x; full_cov=true)]: (mu[B,M], cov[B,M,M]), cov = K** - V^T V, symmetric
+        and not clamped; NaN rows for the slots that failed in that run."""
+        mu = np.empty((self.B, self.M))
+        cov = np.empty((self.B, self.M, self.M))
+        L.check(L.lib.gprx_batch_predict_cov(self.h, L.dptr(mu), L.dptr(cov)), self.ctx.h)
+        return mu, cov
+
+    def sample(self, Z, raise_on_error: bool = False):
+        """Posterior function draws [ext rand(gp, x, n)] from host standard normals Z, (S, M) shared
+        by the slots or (B, S, M): samples[b, s] = mu_b + L_b z_{b,s} with L_b L_b^T = cov_b +
+        jitter_b I (the jitter ladder of gprx_batch_sample).  Returns (samples[B,S,M], jitter[B]); a
+        slot whose covariance could not be factorised has NaN samples and jitter, and raises
+        NotPositiveDefinite only with raise_on_error (as run); `self.last_sample_status` keeps the
+        per-slot status."""
+        Z = _f64(Z)
+        if Z.ndim == 2:
+            S, zs = Z.shape[0], 0
+        else:
+            assert Z.ndim == 3 and Z.shape[0] == self.B, Z.shape
+            S, zs = Z.shape[1], Z.shape[1] * Z.shape[2]
+        assert Z.shape[-1] == self.M, Z.shape
+        out = np.empty((self.B, S, self.M))
+        jit = np.empty(self.B)
+        st = np.empty(self.B, dtype=np.int32)
+        rc = L.lib.gprx_batch_sample(self.h, L.dptr(Z), int(S), zs, L.dptr(out), L.dptr(jit), L.iptr(st))
+        if rc != L.NOT_POSITIVE_DEFINITE or raise_on_error:
+            L.check(rc, self.ctx.h)
+        self.last_sample_status = st
+        return out, jit
+
     def alpha(self):
         """alpha = K^-1 (y - mean) per slot from the last factorisation (gp.alpha); NaN rows for the
         slots that failed in it."""

@@ -150,24 +150,47 @@ class GPE:
     update_target = update_mll
     update_target_and_dtarget = update_mll_and_dmll
 
-    def predict_f(self, xs):
-        """(μ_f, σ²_f) per test column, full_cov=false [ext predict_f]."""
+    def _test_columns(self, xs):
         xs = np.asarray(xs, dtype=np.float64)
         if xs.ndim == 1:
             xs = xs[:, None]
         if xs.shape[0] != self.dim:
             raise ValueError("test inputs have the wrong dimension")
+        return xs
+
+    def predict_f(self, xs, full_cov: bool = False):
+        """(μ_f, σ²_f) per test column; full_cov=True: (μ_f, Σ_f) with the joint M x M covariance
+        [ext predict_f(gp, x; full_cov)]."""
+        xs = self._test_columns(xs)
         self._batch.set_test(xs)
+        if full_cov:
+            mu, cov = self._batch.predict_cov()
+            return mu[0].copy(), cov[0].copy()
         mu, var = self._batch.predict()
         return mu[0].copy(), var[0].copy()
 
-    def predict_y(self, xs):
-        """predict_f + prior mean, variance + exp(2 logNoise)  [ext predict_y]."""
+    def predict_y(self, xs, full_cov: bool = False):
+        """predict_f + prior mean, variance (full_cov: the covariance's diagonal) + exp(2 logNoise)
+        [ext predict_y]."""
         xs = np.asarray(xs, dtype=np.float64)
         if xs.ndim == 1:
             xs = xs[:, None]
-        mu, var = self.predict_f(xs)
+        mu, var = self.predict_f(xs, full_cov=full_cov)
+        if full_cov:
+            var[np.diag_indices_from(var)] += math.exp(2.0 * self.logNoise)
+            return mu + self.mean.mean(xs), var
         return mu + self.mean.mean(xs), var + math.exp(2.0 * self.logNoise)
+
+    def rand(self, xs, n: int = 1, rng=None):
+        """n draws of the posterior function at the columns of xs, (M, n) [ext rand(gp, x, n)]:
+        f-space plus the prior mean.  The standard normals come from `rng` (numpy Generator; default
+        a fresh default_rng()) on the host; the covariance, its factor and mu + L z run on the device."""
+        xs = self._test_columns(xs)
+        rng = rng if rng is not None else np.random.default_rng()
+        Z = rng.standard_normal((int(n), xs.shape[1]))
+        self._batch.set_test(xs)
+        smp, _ = self._batch.sample(Z, raise_on_error=True)
+        return (smp[0] + self.mean.mean(xs)[None, :]).T.copy()
 
     def predict_y_mean(self, xs):
         """predict_y(gp, obs)[1] without the variance: the rollout call of
@@ -187,9 +210,13 @@ def GP(x, y, mean, kernel, logNoise: float = -2.0, ctx: Context | None = None) -
     return GPE(x, y, mean, kernel, logNoise, ctx=ctx)
 
 
-def predict_y(gp: GPE, xs):
-    return gp.predict_y(xs)
+def predict_y(gp: GPE, xs, full_cov: bool = False):
+    return gp.predict_y(xs, full_cov=full_cov)
 
 
-def predict_f(gp: GPE, xs):
-    return gp.predict_f(xs)
+def predict_f(gp: GPE, xs, full_cov: bool = False):
+    return gp.predict_f(xs, full_cov=full_cov)
+
+
+def rand(gp: GPE, xs, n: int = 1, rng=None):
+    return gp.rand(xs, n, rng)

@@ -8,6 +8,8 @@ experiment scripts (examples/noise.jl, examples/hyperparameter.jl) stay textuall
     GP(X, y, mean, SEArd(...))            -> gprx_gp_create + gprx_gp_lml   (CPnoise.jl:40)
     optimize!(gp, LBFGS(...), Options())  -> gprx_gp_lml / gprx_gp_lml_grad per evaluation
     predict_y(gp, x*)                     -> gprx_gp_predict                 (predictdynamics.jl:13)
+    predict_f(gp, x*; full_cov=true)      -> gprx_gp_predict_cov
+    rand(gp, x*, n)                       -> gprx_gp_sample (randn on the Julia side)
 
 plus `GPRx.optimize_all!(gps)`: the loop `for gp in gps; optimize!(gp, LBFGS(linesearch =
 BackTracking(order=2)), Optim.Options(time_limit=10.)); end` of CPnoise.jl:37-43 as ONE
@@ -22,6 +24,7 @@ module GPRx
 using GaussianProcesses
 using GaussianProcesses: GPE, SEArd, Mean
 using LinearAlgebra
+using Random
 
 const LIB = joinpath(@__DIR__, "..", "lib", "libgprx.so")
 const ABI = Cint(3)  # include/gprx.h GPRX_ABI_VERSION these ccall signatures follow
@@ -109,7 +112,7 @@ function evaluate!(gp::GPE, flags::Integer)
 end
 
 # gp.cK (the host PDMat of K and its Cholesky factor) is not maintained by the device path: the
-# factorisation stays in HBM.  Code that reads it (full-covariance prediction, rand, ...) calls
+# factorisation stays in HBM.  Code that reads it directly calls
 # materialize!(gp) first, which runs GaussianProcesses' own update_cK! / update_mll! on the host
 # once at the current hyperparameters (O(N^3) on the CPU, on request only).
 function materialize!(gp::GPE)
@@ -137,18 +140,36 @@ function GaussianProcesses.update_target_and_dtarget!(gp::GPE{<:Any,<:Any,<:Mean
 end
 
 function GaussianProcesses.predict_f(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, x::AbstractMatrix; full_cov::Bool=false)
-    if full_cov  # the M x M posterior covariance: GaussianProcesses' own host method on gp.cK
-        materialize!(gp)
-        return invoke(GaussianProcesses.predict_f, Tuple{GPE,AbstractMatrix}, gp, x; full_cov=true)
-    end
     xs = Matrix{Float64}(x)
     M = size(xs, 2)
+    if full_cov  # the M x M posterior covariance K** - V'V on the device (symmetric, not clamped)
+        mu = zeros(M)
+        cov = zeros(M, M)
+        check(ccall((:gprx_gp_predict_cov, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}),
+                    handle(gp).ptr, xs, M, mu, cov), gp)
+        return mu .+ GaussianProcesses.mean(gp.mean, xs), cov
+    end
     mu = zeros(M)
     var = zeros(M)
     check(ccall((:gprx_gp_predict, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}),
                 handle(gp).ptr, xs, M, mu, var), gp)
     return mu .+ GaussianProcesses.mean(gp.mean, xs), var   # predict_y adds exp(2 logNoise)
 end
+
+# rand(gp, x, n): n draws of the posterior function at the columns of x, M x n.  The standard
+# normals are drawn here (randn); the covariance, its factor (with gprx's own jitter ladder, see
+# include/gprx.h) and mu + L z run on the device.  f-space plus the prior mean.
+function Random.rand(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, x::AbstractMatrix, n::Int)
+    xs = Matrix{Float64}(x)
+    M = size(xs, 2)
+    Z = randn(M, n)              # column s = one draw: the ABI's [S][M] row-major
+    out = zeros(M, n)
+    jit = Ref{Float64}(0.0)
+    check(ccall((:gprx_gp_sample, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Ref{Float64}),
+                handle(gp).ptr, xs, M, Z, n, out, jit), gp)
+    return out .+ GaussianProcesses.mean(gp.mean, xs)
+end
+Random.rand(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, x::AbstractMatrix) = vec(rand(gp, x, 1))
 
 # predictdynamicsmin (examples/utils/predictdynamics.jl:30-102) for all test observations of one
 # trial in one device launch.  `gps` must be MeanZero GPEs evaluated on this thread's context (the

@@ -13,6 +13,8 @@
  *   gprx_gp_lml        update_mll! inside GP()/optimize! value evaluations   [ext] CPnoise.jl:40-41
  *   gprx_gp_lml_grad   update_mll! + update_dmll! (one LBFGS evaluation)     [ext] CPnoise.jl:41
  *   gprx_gp_predict    predict_f / predict_y(gp, x*)  examples/utils/predictdynamics.jl:13
+ *   gprx_gp_predict_cov, gprx_gp_sample   [ext] predict_f(gp, x; full_cov=true), rand(gp, x, n): on
+ *                      every GPE (CPnoise.jl:40); the reference's scripts use the mean only
  *   gprx_rollout_min   predictdynamicsmin             examples/utils/predictdynamics.jl:30-102
  *   gprx_batch_*       the G per-output GPs of a trial (CPnoise.jl:37-43) and the trial loop
  *                      (examples/parallel/core.jl:28) evaluated as one device batch
@@ -152,6 +154,43 @@ int gprx_batch_dims(const gprx_batch* batch, int* B, int* d, int* N, int* M_max)
  * that evaluation was not GPRX_OK has no alpha: its N entries are NaN.                          */
 int gprx_batch_alpha(gprx_batch* batch, double* alpha);
 
+/* ---- joint predictive covariance and posterior samples ------------------------------------- */
+/* [ext] predict_f(gp, x; full_cov=true) and rand(gp, x, n) of GaussianProcesses 0.12.4, which every
+ * GPE the reference builds carries (examples/maximal_coordinates/CPnoise.jl:40); the reference's
+ * own scripts use only the mean (examples/utils/predictdynamics.jl:13).
+ *   Sigma = K**(Xs, Xs) - V^T V,  V = L^-1 K*   (f-space: no noise, no prior mean; K** in the
+ *   context's distance mode; NOT clamped, unlike var; bitwise symmetric).
+ * A slot whose last evaluation failed gets NaN in its mu, cov and samples rows (as
+ * gprx_batch_alpha); the other slots are unaffected.  GPRX_NOT_READY before a successful
+ * factorisation or with no test points set; GPRX_INVALID_ARGUMENT for a NULL cov, Z or samples,
+ * S < 1, Mpad^2 * 8 beyond the 32-bit addressing range (Mpad: M_max rounded up to 64), and, for
+ * the sample calls, M > 1024 (a limit of the single-workgroup factorisation).
+ * The workspace (gprx_batch_cov_bytes) is allocated by the first of these calls on a batch, not by
+ * gprx_batch_create, and freed with the batch; when it cannot be allocated the call returns
+ * GPRX_OUT_OF_MEMORY and the batch stays usable.  The launches go straight on the context stream
+ * (they are not part of the captured evaluation graphs).                                        */
+/* f-space joint posterior at the batch's test points from the last factorisation:
+ * mu[B*M] (may be NULL), cov[B*M*M] (slot b at cov + b*M*M, symmetric).                         */
+int gprx_batch_predict_cov(gprx_batch* batch, double* mu, double* cov);
+/* samples[(b*S + s)*M + m] = mu_b[m] + (L_b z_{b,s})[m],  L_b L_b^T = Sigma_b + jitter_b I.
+ * Z: host, S*M standard normals per slot at Z + b*z_slot_stride (0 = shared).  Self-contained:
+ * it recomputes mu and Sigma itself.  jitter[B], status[B] may be NULL.
+ * The factor of Sigma_b (lower Cholesky, substitution in the panel solves, no explicit inverse):
+ * tau_b = (N + M) * 2^-52 * sigma_f^2 is the rounding bound of Sigma's own entries; a pivot fails
+ * when it is not finite or <= tau_b.  Attempt 0 adds no jitter, attempts k = 1..8 add 10^k tau_b to
+ * the diagonal; the first attempt whose pivots all pass wins and jitter[b] reports its value (0 or
+ * 10^k tau_b).  If all nine fail, status[b] = GPRX_NOT_POSITIVE_DEFINITE, jitter[b] and the slot's
+ * samples are NaN, and the call returns the first failing slot's status.  This ladder is gprx's own
+ * rule: GaussianProcesses.jl was not available to compare its rand() against.                     */
+int gprx_batch_sample(gprx_batch* batch, const double* Z, int S, int64_t z_slot_stride, double* samples,
+                      double* jitter, int* status);
+/* device bytes the two calls allocate on first use, on top of gprx_batch_bytes (host arithmetic):
+ * 8 B (Npad Mpad + 2 Mpad^2) for V^T, Sigma and its factor, plus the staging term
+ * 8 B 2 Mpad^2 + 12 B (the device Z and sample buffers, Mpad vectors per slot a pass, and the
+ * per-slot jitter and status).  GPRX_INVALID_ARGUMENT for a NULL bytes, sizes gprx_batch_create
+ * refuses, or Mpad^2 * 8 beyond the addressing range.                                            */
+int gprx_batch_cov_bytes(int B, int N, int M_max, uint64_t* bytes);
+
 /* ---- hyper-parameter optimisation on the device ------------------------------------------- */
 /* GaussianProcesses.optimize!(gp, LBFGS(linesearch=BackTracking(order=2)), Optim.Options(...))
  * (examples/maximal_coordinates/CPnoise.jl:41 and its 15 siblings) for every slot of a batch:
@@ -224,6 +263,11 @@ int gprx_gp_lml_grad(gprx_gp* gp, const double* theta, double* mll, double* grad
 /* f-space predictive mean (k*^T alpha) and variance (max(k** - |L^-1 k*|^2, 0)) at the
  * factorisation of the last lml call; var may be NULL.                                          */
 int gprx_gp_predict(gprx_gp* gp, const double* Xs, int M, double* mu_f, double* var_f);
+/* [ext] predict_f(gp, x; full_cov=true): mu_f[M] (may be NULL), cov[M*M]; and rand(gp, x, n) in
+ * f-space: samples[S*M] from Z[S*M] host standard normals, jitter (may be NULL) as
+ * gprx_batch_sample (whose jitter rule is gprx's own).                                          */
+int gprx_gp_predict_cov(gprx_gp* gp, const double* Xs, int M, double* mu, double* cov);
+int gprx_gp_sample(gprx_gp* gp, const double* Xs, int M, const double* Z, int S, double* samples, double* jitter);
 
 /* the single GP's underlying batch of one (slot 0), e.g. for gprx_rollout_min              */
 gprx_batch* gprx_gp_batch(gprx_gp* gp);
