@@ -62,7 +62,6 @@ struct gprx_ctx {
 struct gprx_batch {
   gprx_ctx* ctx = nullptr;
   DevBatch db{};
-  std::vector<void*> allocs;
   double* h_params = nullptr;  // pinned
   double* h_out = nullptr;     // pinned, B*(d+3)
   double* h_mu = nullptr;      // pinned, B*Mpad
@@ -157,92 +156,146 @@ void collect(gprx_ctx* c) {
   c->pending.clear();
 }
 
-template <class T>
-int dalloc(gprx_batch* b, T** p, size_t count) {
-  void* q = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc(&q, count * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // clear the runtime's sticky error: later calls check hipGetLastError
-    *p = nullptr;
-    return set_err(b->ctx, e == hipErrorOutOfMemory ? GPRX_OUT_OF_MEMORY : GPRX_DEVICE_ERROR,
-                   std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  b->allocs.push_back(q);
-  *p = (T*)q;
-  return GPRX_OK;
-}
-
-void free_test(gprx_batch* b);
-
 // The GEMM cores, the Gram and the LINV21 store address their operands through buffer resources of
 // 0x7ffffff0 bytes from a tile origin, with 32-bit byte offsets (gprx_kernels.hip buffer_rsrc,
 // core_ptr): a K walk spans up to Npad columns of ld = Npad (the factorisation) or Npad rows of
 // ld = Mpad (the prediction variance's K*^T).  Beyond that range a load would silently read 0, so
 // such sizes are refused (N <= 16320 at M <= Npad).
 constexpr size_t BUF_LIMIT = 0x7ffffff0;
-bool sizes_addressable(size_t Npad, size_t Mpad) { return Npad * std::max(Npad, Mpad) * sizeof(double) < BUF_LIMIT; }
 size_t pad64(size_t n) { return (n + TS - 1) / TS * TS; }
-
-// Device bytes of a batch's test-point buffers (alloc_test) and of the whole batch
-// (gprx_batch_create); the same expressions as the allocations
-size_t test_bytes(size_t B, size_t d, size_t Npad, size_t Mpad) {
-  const size_t nt = Npad / TS;
-  return sizeof(double) * (B * Mpad * d + B * Npad * Mpad + 2 * B * nt * Mpad + 2 * B * Mpad);
+size_t test_capacity(int M_max) { return std::max<size_t>(pad64(M_max), TS); }  // Mpad: at least one tile
+bool sizes_addressable(int N, int M_max) {
+  const size_t Npad = pad64(N);
+  return Npad * std::max(Npad, test_capacity(M_max)) * sizeof(double) < BUF_LIMIT;
 }
-size_t batch_bytes(size_t B, int d, size_t Npad, size_t Mpad) {
-  const size_t nt = Npad / TS, mat = Npad * Npad, xs = (size_t)(d | 1);
-  int ngu = 0, nimg = 0;
-  const size_t nlj = (size_t)std::max(gprx::lauum_plan((int)nt, d, &ngu, &nimg, nullptr), 0);
-  const size_t dbl = B * Npad * d + B * Npad * xs + B * Npad + 5 * B * mat + B * Npad + B * 2 * nt * Npad + B * Npad +
-                     B * (d + 4) + B * (d + 2) + B * nt + B * (size_t)ngu * (d + 2) + B * (d + 3);
-  const size_t ints = 2 * B + 2 * gprx::LU * nlj + B;
-  return dbl * sizeof(double) + ints * sizeof(int) + test_bytes(B, d, Npad, Mpad);
-}
+bool cov_addressable(int M_max) { return test_capacity(M_max) * test_capacity(M_max) * sizeof(double) < BUF_LIMIT; }
 
-int alloc_test(gprx_batch* b, int M_max) {
-  DevBatch& db = b->db;
+// The dimensions every buffer size follows from (sizes_addressable first): the training side once,
+// at creation; the test side whenever the capacity for test points changes.
+void set_train_dims(DevBatch& db, int B, int d, int N) {
+  db.B = B;
+  db.d = d;
+  db.N = N;
+  db.Npad = (int)pad64(N);
+  db.nt = db.Npad / TS;
+  db.ntl = db.nt * (db.nt + 1) / 2;
+  db.ld = db.Npad;
+  db.mat = (size_t)db.Npad * db.Npad;
+  db.xs = d | 1;
+  db.pst = d + 4;
+  db.gps = d + 2;
+  db.nlj = gprx::lauum_plan(db.nt, d, &db.ngu, &db.nimg, nullptr);
+}
+void set_test_dims(DevBatch& db, int M_max) {
   db.M = 0;
-  db.Mpad = ((M_max + TS - 1) / TS) * TS;
-  if (db.Mpad == 0) db.Mpad = TS;
-  if (!sizes_addressable(db.Npad, db.Mpad))
-    return set_err(b->ctx, GPRX_INVALID_ARGUMENT, "test points: Npad * max(Npad, Mpad) * 8 exceeds the 2 GiB buffer range");
+  db.Mpad = (int)test_capacity(M_max);
   db.mt = db.Mpad / TS;
-  const size_t B = db.B;
-  int rc;
-  if ((rc = dalloc(b, &db.Xs, B * db.Mpad * db.d))) return rc;
-  if ((rc = dalloc(b, &db.KsT, B * (size_t)db.Npad * db.Mpad))) return rc;
-  if ((rc = dalloc(b, &db.mu_part, B * db.nt * (size_t)db.Mpad))) return rc;
-  if ((rc = dalloc(b, &db.var_part, B * db.nt * (size_t)db.Mpad))) return rc;
-  if ((rc = dalloc(b, &db.out_mu, B * db.Mpad))) return rc;
-  if ((rc = dalloc(b, &db.out_var, B * db.Mpad))) return rc;
-  if (hipHostMalloc((void**)&b->h_mu, B * db.Mpad * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&b->h_var, B * db.Mpad * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return GPRX_OUT_OF_MEMORY;
+}
+
+// One buffer of a batch: where its pointer lives, elements, element size, device or pinned host
+// memory, zero-filled when allocated.  A batch's buffers come in three groups, each listed by one
+// function from the batch's dimensions alone (the pointers may be null): allocation, release and
+// gprx_batch_bytes / gprx_batch_cov_bytes all read these lists and nothing else.
+struct Buf {
+  void** p;
+  size_t count, size;
+  bool pinned, zero;
+};
+template <class T>
+Buf dev(T*& p, size_t count, bool zero = false) {
+  return {(void**)&p, count, sizeof(T), false, zero};
+}
+template <class T>
+Buf pin(T*& p, size_t count, size_t size = sizeof(T)) {
+  return {(void**)&p, count, size, true, false};
+}
+using BufList = std::vector<Buf>;
+
+// created with the batch.  Zero padding of X / Y (pad columns never enter a result; kept finite)
+// and of the matrices the factorisation writes in part
+BufList train_bufs(gprx_batch& b) {
+  DevBatch& db = b.db;
+  const size_t B = db.B, Np = db.Npad, d = db.d;
+  return {dev(db.X, B * Np * d, true), dev(db.Xc, B * Np * db.xs), dev(db.Y, B * Np, true), dev(db.K, B * db.mat),
+          dev(db.S, B * db.mat, true), dev(db.Lw, B * db.mat, true), dev(db.Linv, B * db.mat, true),
+          dev(db.Mt, B * db.mat, true), dev(db.z, B * Np), dev(db.zp, B * 2 * db.nt * Np), dev(db.alpha, B * Np),
+          dev(db.params, B * db.pst), dev(db.theta, B * (d + 2)), dev(db.logdet_part, B * db.nt),
+          dev(db.grad_part, B * db.ngu * db.gps), dev(db.out, B * (d + 3)), dev(db.status, 2 * B) /* status, info */,
+          dev(db.lauum_order, 2 * gprx::LU * (size_t)std::max(db.nlj, 0)), dev(b.opt_active, B),
+          pin(b.h_params, B * db.pst), pin(b.h_out, B * (d + 3)), pin(b.h_status, 2 * B)};
+}
+// sized by Mpad, regrown by gprx_batch_set_test
+BufList test_bufs(gprx_batch& b) {
+  DevBatch& db = b.db;
+  const size_t B = db.B, Mp = db.Mpad;
+  return {dev(db.Xs, B * Mp * db.d, true), dev(db.KsT, B * db.Npad * Mp), dev(db.mu_part, B * db.nt * Mp),
+          dev(db.var_part, B * db.nt * Mp), dev(db.out_mu, B * Mp), dev(db.out_var, B * Mp),
+          pin(b.h_mu, B * Mp), pin(b.h_var, B * Mp)};
+}
+// the joint-covariance workspace, sized by Mpad, allocated on first use (cov_alloc): V^T, Sigma, its
+// factor; the Z and sample buffers of a pass; the per-slot jitter and status and their host mirror
+BufList cov_bufs(gprx_batch& b) {
+  const DevBatch& db = b.db;
+  const size_t B = db.B, mm = (size_t)db.Mpad * db.Mpad;
+  return {dev(b.cov_vt, B * db.Npad * db.Mpad), dev(b.cov_sig, B * mm), dev(b.cov_f, B * mm), dev(b.cov_z, B * mm),
+          dev(b.cov_smp, B * mm), dev(b.cov_jit, B), dev(b.cov_st, B), pin(b.h_cov, B, sizeof(double) + sizeof(int))};
+}
+
+void bufs_free(const BufList& l) {
+  for (const Buf& u : l) {
+    if (*u.p) (void)(u.pinned ? hipHostFree(*u.p) : hipFree(*u.p));
+    *u.p = nullptr;
   }
-  (void)hipMemset(db.Xs, 0, B * db.Mpad * db.d * sizeof(double));
+}
+// All of a list (its pointers null on entry), or none of it: a failure frees what it got.  An empty
+// buffer still gets one element, so that its pointer is valid.
+int bufs_alloc(gprx_ctx* c, const BufList& l) {
+  for (const Buf& u : l) {
+    const size_t bytes = std::max<size_t>(u.count, 1) * u.size;
+    hipError_t e = u.pinned ? hipHostMalloc(u.p, bytes) : hipMalloc(u.p, bytes);
+    int rc = GPRX_OK;
+    if (e != hipSuccess) {
+      *u.p = nullptr;
+      rc = u.pinned ? set_err(c, GPRX_OUT_OF_MEMORY, "hipHostMalloc failed")
+                    : set_err(c, e == hipErrorOutOfMemory ? GPRX_OUT_OF_MEMORY : GPRX_DEVICE_ERROR,
+                              std::string("hipMalloc: ") + hipGetErrorString(e));
+    } else if (u.zero && hipMemset(*u.p, 0, bytes) != hipSuccess) {
+      rc = GPRX_DEVICE_ERROR;
+    }
+    if (rc) {
+      (void)hipGetLastError();  // clear the runtime's sticky error: later calls check hipGetLastError
+      bufs_free(l);
+      return rc;
+    }
+  }
   return GPRX_OK;
 }
-
-void release_ptr(gprx_batch* b, void* p) {
-  for (auto it = b->allocs.begin(); it != b->allocs.end(); ++it)
-    if (*it == p) {
-      (void)hipFree(p);
-      b->allocs.erase(it);
-      return;
-    }
+size_t bufs_device_bytes(const BufList& l) {
+  size_t n = 0;
+  for (const Buf& u : l)
+    if (!u.pinned) n += u.count * u.size;
+  return n;
 }
 
-void free_test(gprx_batch* b) {
-  DevBatch& db = b->db;
-  void* ps[] = {db.Xs, db.KsT, db.mu_part, db.var_part, db.out_mu, db.out_var};
-  for (void* p : ps)
-    if (p) release_ptr(b, p);
-  db.Xs = db.KsT = db.mu_part = db.var_part = db.out_mu = db.out_var = nullptr;
-  if (b->h_mu) (void)hipHostFree(b->h_mu);
-  if (b->h_var) (void)hipHostFree(b->h_var);
-  b->h_mu = b->h_var = nullptr;
+// The joint-covariance workspace goes with the test buffers it was sized for.
+void cov_free(gprx_batch* b) {
+  bufs_free(cov_bufs(*b));
+  b->cov_mpad = 0;
+}
+// A batch without test buffers, and saying so: the state after a regrow that failed.  A later
+// gprx_batch_set_test allocates afresh; until then there is nothing to predict.
+void drop_test(gprx_batch* b) {
+  bufs_free(test_bufs(*b));
+  cov_free(b);
+  b->db.M = b->db.Mpad = b->db.mt = 0;
+  b->have_test = false;
+}
+// The test buffers for M_max points (none held on entry); a failure leaves drop_test's state.
+int alloc_test(gprx_batch* b, int M_max) {
+  set_test_dims(b->db, M_max);
+  const int rc = bufs_alloc(b->ctx, test_bufs(*b));
+  if (rc) drop_test(b);
+  return rc;
 }
 
 int copy_in(gprx_ctx* c, void* dst, const void* src, size_t bytes, int mem) {
@@ -379,9 +432,47 @@ int run_eval(gprx_batch* b, bool want_grad, bool want_pred, bool factor) {
   return GPRX_OK;
 }
 
-// Per-call launch geometry from the context options and the batch size.
-void set_geometry(const gprx_ctx* c, DevBatch& db) {
+// Per-call settings of an evaluation: the context's distance mode, whether a predictive variance
+// is wanted, and the launch geometry from the context options and the batch size.
+void set_geometry(const gprx_ctx* c, DevBatch& db, bool want_var) {
+  db.dist_mode = c->dist_mode;
+  db.want_var = want_var;
   db.small_n = c->small_n > 0 ? c->small_n : (db.B >= 32 ? 4 : 64);  // small batches: more, smaller units
+}
+
+// ---- one-call workspaces: a block carved into 16-byte aligned pieces, and its owner --------------
+// take<T>(n) reserves n Ts and returns their byte offset; size is the block's size so far.  at<T>
+// is the piece's address once the block exists.
+struct Layout {
+  size_t size = 0;
+  template <class T>
+  size_t take(size_t n) {
+    const size_t o = size;
+    size = (o + n * sizeof(T) + 15) / 16 * 16;
+    return o;
+  }
+};
+template <class T>
+T* at(char* base, size_t offset) {
+  return (T*)(base + offset);
+}
+struct DevFree {
+  void operator()(char* p) const { (void)hipFree(p); }
+};
+struct PinFree {
+  void operator()(char* p) const { (void)hipHostFree(p); }
+};
+using DevBlock = std::unique_ptr<char, DevFree>;
+using PinBlock = std::unique_ptr<char, PinFree>;
+DevBlock dev_block(size_t bytes) {  // null on failure
+  char* p = nullptr;
+  if (hipMalloc((void**)&p, bytes) != hipSuccess) (void)hipGetLastError(), p = nullptr;
+  return DevBlock(p);
+}
+PinBlock pin_block(size_t bytes) {
+  char* p = nullptr;
+  if (hipHostMalloc((void**)&p, bytes) != hipSuccess) (void)hipGetLastError(), p = nullptr;
+  return PinBlock(p);
 }
 
 }  // namespace
@@ -522,7 +613,7 @@ int gprx_batch_create(gprx_ctx* c, int B, int d, int N, int M_max, gprx_batch** 
   *out = nullptr;
   if (B < 1 || d < 1 || d > gprx::DMAX || N < 1 || M_max < 0)
     return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_create: need B>=1, 1<=d<=64, N>=1, M_max>=0");
-  if (!sizes_addressable(pad64(N), std::max<size_t>(pad64(M_max), TS)))
+  if (!sizes_addressable(N, M_max))
     return set_err(c, GPRX_INVALID_ARGUMENT,
                    "gprx_batch_create: Npad * max(Npad, Mpad) * 8 must stay below the 2 GiB buffer range (N <= 16320)");
   std::lock_guard<std::mutex> g(c->mu);
@@ -531,18 +622,7 @@ int gprx_batch_create(gprx_ctx* c, int B, int d, int N, int M_max, gprx_batch** 
   b->ctx = c;
   c->batches.insert(b);
   DevBatch& db = b->db;
-  db.B = B;
-  db.d = d;
-  db.N = N;
-  db.Npad = ((N + TS - 1) / TS) * TS;
-  db.nt = db.Npad / TS;
-  db.ntl = db.nt * (db.nt + 1) / 2;
-  db.ld = db.Npad;
-  db.mat = (size_t)db.Npad * db.Npad;
-  db.pst = d + 4;
-  db.gps = d + 2;
-  db.nlj = gprx::lauum_plan(db.nt, d, &db.ngu, &db.nimg, nullptr);
-  const size_t Bs = B;
+  set_train_dims(db, B, d, N);
   int rc = GPRX_OK;
   auto fail = [&](int r) {  // under c->mu: unlink here, free without re-locking
     c->batches.erase(b);
@@ -550,27 +630,8 @@ int gprx_batch_create(gprx_ctx* c, int B, int d, int N, int M_max, gprx_batch** 
     return r;
   };
   if (db.nlj < 1) return fail(set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_create: lauum plan failed"));
-  if ((rc = dalloc(b, &db.X, Bs * db.Npad * d))) return fail(rc);
-  db.xs = d | 1;
-  if ((rc = dalloc(b, &db.Xc, Bs * db.Npad * db.xs))) return fail(rc);
-  if ((rc = dalloc(b, &db.Y, Bs * db.Npad))) return fail(rc);
-  if ((rc = dalloc(b, &db.K, Bs * db.mat))) return fail(rc);
-  if ((rc = dalloc(b, &db.S, Bs * db.mat))) return fail(rc);
-  if ((rc = dalloc(b, &db.Lw, Bs * db.mat))) return fail(rc);
-  if ((rc = dalloc(b, &db.Linv, Bs * db.mat))) return fail(rc);
-  if ((rc = dalloc(b, &db.Mt, Bs * db.mat))) return fail(rc);
-  if ((rc = dalloc(b, &db.z, Bs * db.Npad))) return fail(rc);
-  if ((rc = dalloc(b, &db.zp, Bs * 2 * db.nt * (size_t)db.Npad))) return fail(rc);
-  if ((rc = dalloc(b, &db.alpha, Bs * db.Npad))) return fail(rc);
-  if ((rc = dalloc(b, &db.params, Bs * db.pst))) return fail(rc);
-  if ((rc = dalloc(b, &db.theta, Bs * (d + 2)))) return fail(rc);
-  if ((rc = dalloc(b, &db.logdet_part, Bs * db.nt))) return fail(rc);
-  if ((rc = dalloc(b, &db.grad_part, Bs * db.ngu * db.gps))) return fail(rc);
-  if ((rc = dalloc(b, &db.out, Bs * (d + 3)))) return fail(rc);
-  if ((rc = dalloc(b, &db.status, 2 * Bs))) return fail(rc);
-  db.info = db.status + Bs;
-  if ((rc = dalloc(b, &db.lauum_order, 2 * gprx::LU * (size_t)db.nlj))) return fail(rc);
-  if ((rc = dalloc(b, &b->opt_active, Bs))) return fail(rc);
+  if ((rc = bufs_alloc(c, train_bufs(*b)))) return fail(rc);
+  db.info = db.status + B;
   {
     std::vector<int> ord(2 * gprx::LU * (size_t)db.nlj);
     int nu, ni;
@@ -579,20 +640,6 @@ int gprx_batch_create(gprx_ctx* c, int B, int d, int N, int M_max, gprx_batch** 
       return fail(GPRX_DEVICE_ERROR);
   }
   if ((rc = alloc_test(b, M_max))) return fail(rc);
-  if (hipHostMalloc((void**)&b->h_params, Bs * db.pst * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&b->h_out, Bs * (d + 3) * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&b->h_status, 2 * Bs * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(set_err(c, GPRX_OUT_OF_MEMORY, "hipHostMalloc failed"));
-  }
-  // zero padding of X / Y (pad columns never enter a result; kept finite)
-  if (hipMemset(db.X, 0, Bs * db.Npad * d * sizeof(double)) != hipSuccess ||
-      hipMemset(db.Y, 0, Bs * db.Npad * sizeof(double)) != hipSuccess ||
-      hipMemset(db.Lw, 0, Bs * db.mat * sizeof(double)) != hipSuccess ||
-      hipMemset(db.Linv, 0, Bs * db.mat * sizeof(double)) != hipSuccess ||
-      hipMemset(db.Mt, 0, Bs * db.mat * sizeof(double)) != hipSuccess ||
-      hipMemset(db.S, 0, Bs * db.mat * sizeof(double)) != hipSuccess)
-    return fail(GPRX_DEVICE_ERROR);
   *out = b;
   return GPRX_OK;
 }
@@ -604,13 +651,8 @@ static void batch_free(gprx_batch* b) {
   if (b->ctx) (void)hipStreamSynchronize(b->ctx->stream);
   for (int i = 0; i < 4; ++i)
     if (b->gvalid[i]) (void)hipGraphExecDestroy(b->gexec[i]);
-  for (void* p : b->allocs) (void)hipFree(p);
-  if (b->h_params) (void)hipHostFree(b->h_params);
-  if (b->h_out) (void)hipHostFree(b->h_out);
-  if (b->h_mu) (void)hipHostFree(b->h_mu);
-  if (b->h_var) (void)hipHostFree(b->h_var);
-  if (b->h_status) (void)hipHostFree(b->h_status);
-  if (b->h_cov) (void)hipHostFree(b->h_cov);
+  bufs_free(train_bufs(*b));
+  drop_test(b);
   delete b;
 }
 
@@ -635,9 +677,11 @@ int gprx_batch_dims(const gprx_batch* b, int* B, int* d, int* N, int* M_max) {
 int gprx_batch_bytes(int B, int d, int N, int M_max, uint64_t* bytes) {
   if (bytes) *bytes = 0;
   if (!bytes || B < 1 || d < 1 || d > gprx::DMAX || N < 1 || M_max < 0) return GPRX_INVALID_ARGUMENT;
-  const size_t Npad = pad64(N), Mpad = std::max<size_t>(pad64(M_max), TS);
-  if (!sizes_addressable(Npad, Mpad)) return GPRX_INVALID_ARGUMENT;
-  *bytes = batch_bytes((size_t)B, d, Npad, Mpad);
+  if (!sizes_addressable(N, M_max)) return GPRX_INVALID_ARGUMENT;
+  gprx_batch b;  // dimensions only: what gprx_batch_create would allocate for them
+  set_train_dims(b.db, B, d, N);
+  set_test_dims(b.db, M_max);
+  *bytes = bufs_device_bytes(train_bufs(b)) + bufs_device_bytes(test_bufs(b));
   return GPRX_OK;
 }
 
@@ -679,11 +723,13 @@ int gprx_batch_set_test(gprx_batch* b, const double* Xs, int M, int64_t xss, int
   std::lock_guard<std::mutex> g(c->mu);
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   DevBatch& db = b->db;
-  if (M > db.Mpad) {
+  if (M > db.Mpad || !db.Xs) {  // grow the capacity (or allocate afresh after a failed regrow)
+    if (!sizes_addressable(db.N, M))
+      return set_err(c, GPRX_INVALID_ARGUMENT, "test points: Npad * max(Npad, Mpad) * 8 exceeds the 2 GiB buffer range");
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_test(b);
+    bufs_free(test_bufs(*b));
     int rc = alloc_test(b, M);
-    if (rc) return rc;
+    if (rc) return rc;  // no test buffers, no test points, no covariance workspace (drop_test)
   }
   HIPCHK(c, hipMemsetAsync(db.Xs, 0, (size_t)db.B * db.Mpad * db.d * sizeof(double), c->stream));
   int rc;
@@ -716,6 +762,31 @@ static bool out_direct(gprx_ctx* c, double* dst, const double* src, const DevBat
                           db.B, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
 }
 
+// The predictive outputs of a batch on their way to the caller (NULL: not wanted).  pred_out_queue
+// queues the copies on the context stream, straight into a pinned caller buffer or else into the
+// batch's staging buffers, and reports which went direct; pred_out_unpack, after the stream has been
+// synchronised, copies the staged ones out slot by slot.
+struct PredDirect {
+  bool mu = false, var = false;
+};
+static int pred_out_queue(gprx_batch* b, double* mu, double* var, PredDirect* pd) {
+  gprx_ctx* c = b->ctx;
+  const DevBatch& db = b->db;
+  const size_t bytes = (size_t)db.B * db.Mpad * sizeof(double);
+  pd->mu = mu && out_direct(c, mu, db.out_mu, db);
+  pd->var = var && out_direct(c, var, db.out_var, db);
+  if (mu && !pd->mu) HIPCHK(c, hipMemcpyAsync(b->h_mu, db.out_mu, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (var && !pd->var) HIPCHK(c, hipMemcpyAsync(b->h_var, db.out_var, bytes, hipMemcpyDeviceToHost, c->stream));
+  return GPRX_OK;
+}
+static void pred_out_unpack(const gprx_batch* b, double* mu, double* var, PredDirect pd) {
+  const DevBatch& db = b->db;
+  for (int s = 0; s < db.B; ++s) {
+    if (mu && !pd.mu) memcpy(mu + (size_t)s * db.M, b->h_mu + (size_t)s * db.Mpad, db.M * sizeof(double));
+    if (var && !pd.var) memcpy(var + (size_t)s * db.M, b->h_var + (size_t)s * db.Mpad, db.M * sizeof(double));
+  }
+}
+
 static int batch_predict_locked(gprx_batch* b, double* mu, double* var) {
   gprx_ctx* c = b->ctx;
   DevBatch& db = b->db;
@@ -724,17 +795,11 @@ static int batch_predict_locked(gprx_batch* b, double* mu, double* var) {
   db.want_var = var != nullptr;
   int rc = run_eval(b, false, true, false);
   if (rc) return rc;
-  const bool dmu = mu && out_direct(c, mu, db.out_mu, db), dvar = var && out_direct(c, var, db.out_var, db);
-  if (mu && !dmu)
-    HIPCHK(c, hipMemcpyAsync(b->h_mu, db.out_mu, (size_t)db.B * db.Mpad * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (var && !dvar)
-    HIPCHK(c, hipMemcpyAsync(b->h_var, db.out_var, (size_t)db.B * db.Mpad * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PredDirect pd;
+  if ((rc = pred_out_queue(b, mu, var, &pd))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  for (int s = 0; s < db.B; ++s) {
-    if (mu && !dmu) memcpy(mu + (size_t)s * db.M, b->h_mu + (size_t)s * db.Mpad, db.M * sizeof(double));
-    if (var && !dvar) memcpy(var + (size_t)s * db.M, b->h_var + (size_t)s * db.Mpad, db.M * sizeof(double));
-  }
+  pred_out_unpack(b, mu, var, pd);
   return GPRX_OK;
 }
 
@@ -746,9 +811,7 @@ int gprx_batch_run(gprx_batch* b, const double* theta, unsigned flags, double* m
   if (!b->have_train) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_run before gprx_batch_set_train");
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   DevBatch& db = b->db;
-  db.dist_mode = c->dist_mode;
-  db.want_var = var != nullptr;
-  set_geometry(c, db);
+  set_geometry(c, db, var != nullptr);
   const int d = db.d, B = db.B, np = d + 2;
   // hyper-parameters -> kernel parameters on the device (derive_params: SEArd / GPE's
   // il2 = exp(-2 log ell), sf2 = exp(2 log sf), noise = exp(2 logNoise) + eps()); h_params is the
@@ -765,14 +828,10 @@ int gprx_batch_run(gprx_batch* b, const double* theta, unsigned flags, double* m
   }
   HIPCHK(c, hipMemcpyAsync(b->h_out, db.out, (size_t)B * (d + 3) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(b->h_status, db.status, 2 * (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  bool dmu = false, dvar = false;  // predictive outputs copied straight into pinned caller buffers
+  PredDirect pd;
   if (want_pred) {
-    dmu = mu && out_direct(c, mu, db.out_mu, db);
-    dvar = var && out_direct(c, var, db.out_var, db);
-    if (mu && !dmu)
-      HIPCHK(c, hipMemcpyAsync(b->h_mu, db.out_mu, (size_t)B * db.Mpad * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (var && !dvar)
-      HIPCHK(c, hipMemcpyAsync(b->h_var, db.out_var, (size_t)B * db.Mpad * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    int rc = pred_out_queue(b, mu, var, &pd);
+    if (rc) return rc;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
@@ -785,11 +844,8 @@ int gprx_batch_run(gprx_batch* b, const double* theta, unsigned flags, double* m
     const double* o = b->h_out + (size_t)s * (d + 3);
     if (mll) mll[s] = o[0];
     if (grad && want_grad) memcpy(grad + (size_t)s * np, o + 1, np * sizeof(double));
-    if (want_pred) {
-      if (mu && !dmu) memcpy(mu + (size_t)s * db.M, b->h_mu + (size_t)s * db.Mpad, db.M * sizeof(double));
-      if (var && !dvar) memcpy(var + (size_t)s * db.M, b->h_var + (size_t)s * db.Mpad, db.M * sizeof(double));
-    }
   }
+  if (want_pred) pred_out_unpack(b, mu, var, pd);
   b->factored = true;
   if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_run: ") + gprx_status_string(first));
   return first;
@@ -821,46 +877,16 @@ int gprx_batch_predict(gprx_batch* b, double* mu, double* var) {
 }
 
 // ---- joint predictive covariance and posterior samples (gprx_predcov.h) -------------------------
-// Device bytes of the joint-covariance workspace (cov_alloc): V^T, Sigma, its factor; the Z and
-// sample buffers of a pass and the per-slot jitter and status (the staging term)
-static size_t cov_bytes(size_t B, size_t Npad, size_t Mpad) {
-  return sizeof(double) * B * (Npad * Mpad + 2 * Mpad * Mpad) + sizeof(double) * B * 2 * Mpad * Mpad + B * (sizeof(double) + sizeof(int));
-}
-static bool cov_addressable(size_t Mpad) { return Mpad * Mpad * sizeof(double) < BUF_LIMIT; }
-
-static void cov_free(gprx_batch* b) {
-  void* ps[] = {b->cov_vt, b->cov_sig, b->cov_f, b->cov_z, b->cov_smp, b->cov_jit, b->cov_st};
-  for (void* p : ps)
-    if (p) release_ptr(b, p);
-  b->cov_vt = b->cov_sig = b->cov_f = b->cov_z = b->cov_smp = b->cov_jit = nullptr;
-  b->cov_st = nullptr;
-  if (b->h_cov) (void)hipHostFree(b->h_cov);
-  b->h_cov = nullptr;
-  b->cov_mpad = 0;
-}
-// The workspace for the batch's current Mpad; a failure frees what it got and leaves the batch as
-// it was before the call.
+// The workspace for the batch's current Mpad; a failure frees what it got and leaves the batch
+// without one.
 static int cov_alloc(gprx_batch* b) {
   gprx_ctx* c = b->ctx;
-  const DevBatch& db = b->db;
-  if (b->cov_mpad == db.Mpad) return GPRX_OK;
+  if (b->cov_mpad == b->db.Mpad) return GPRX_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   cov_free(b);
-  const size_t B = db.B, mm = (size_t)db.Mpad * db.Mpad;
-  int rc;
-  if ((rc = dalloc(b, &b->cov_vt, B * db.Npad * db.Mpad)) || (rc = dalloc(b, &b->cov_sig, B * mm)) ||
-      (rc = dalloc(b, &b->cov_f, B * mm)) || (rc = dalloc(b, &b->cov_z, B * mm)) || (rc = dalloc(b, &b->cov_smp, B * mm)) ||
-      (rc = dalloc(b, &b->cov_jit, B)) || (rc = dalloc(b, &b->cov_st, B))) {
-    cov_free(b);
-    return rc;
-  }
-  if (hipHostMalloc((void**)&b->h_cov, B * (sizeof(double) + sizeof(int))) != hipSuccess) {
-    (void)hipGetLastError();
-    b->h_cov = nullptr;
-    cov_free(b);
-    return set_err(c, GPRX_OUT_OF_MEMORY, "hipHostMalloc failed");
-  }
-  b->cov_mpad = db.Mpad;
+  const int rc = bufs_alloc(c, cov_bufs(*b));
+  if (rc) return rc;
+  b->cov_mpad = b->db.Mpad;
   return GPRX_OK;
 }
 
@@ -891,9 +917,11 @@ static void nan_fill(double* p, size_t n) {
 int gprx_batch_cov_bytes(int B, int N, int M_max, uint64_t* bytes) {
   if (bytes) *bytes = 0;
   if (!bytes || B < 1 || N < 1 || M_max < 0) return GPRX_INVALID_ARGUMENT;
-  const size_t Npad = pad64(N), Mpad = std::max<size_t>(pad64(M_max), TS);
-  if (!sizes_addressable(Npad, Mpad) || !cov_addressable(Mpad)) return GPRX_INVALID_ARGUMENT;
-  *bytes = cov_bytes((size_t)B, Npad, Mpad);
+  if (!sizes_addressable(N, M_max) || !cov_addressable(M_max)) return GPRX_INVALID_ARGUMENT;
+  gprx_batch b;  // dimensions only: what cov_alloc would allocate for them
+  set_train_dims(b.db, B, 1, N);  // d does not enter the workspace's sizes
+  set_test_dims(b.db, M_max);
+  *bytes = bufs_device_bytes(cov_bufs(b));
   return GPRX_OK;
 }
 
@@ -1005,9 +1033,7 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
     return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_optimize: bad options");
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   DevBatch& db = b->db;
-  db.dist_mode = c->dist_mode;
-  db.want_var = 0;
-  set_geometry(c, db);
+  set_geometry(c, db, false);
   const int B = db.B, n = db.d + 2;
   gprx::LbArgs a{};
   a.n = n;
@@ -1024,38 +1050,27 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
   a.rho_lo = o.rho_lo;
   // one device block: state, start points, flags, results; one pinned host mirror of the flags
   // and results
-  const size_t wsd = (size_t)B * gprx::lb_ws_doubles(n, o.m), rd = (size_t)B * (n + 1);
-  const size_t nd = wsd + (size_t)B * n + rd, ni = (size_t)B * (gprx::LB_NI + 1 + 4);
-  char* dbuf = nullptr;
-  char* hbuf = nullptr;
-  if (hipMalloc((void**)&dbuf, nd * sizeof(double) + ni * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: workspace");
-  }
-  if (hipHostMalloc((void**)&hbuf, rd * sizeof(double) + (size_t)B * 5 * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(dbuf);
-    return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: host buffer");
-  }
-  struct Free {
-    char *d, *h;
-    ~Free() {
-      (void)hipFree(d);
-      (void)hipHostFree(h);
-    }
-  } fr{dbuf, hbuf};
-  a.ws = (double*)dbuf;
-  double* th0d = a.ws + wsd;
+  const size_t rd = (size_t)B * (n + 1);
+  Layout dl, hl;
+  const size_t o_ws = dl.take<double>((size_t)B * gprx::lb_ws_doubles(n, o.m)), o_th0 = dl.take<double>((size_t)B * n),
+               o_res = dl.take<double>(rd), o_iws = dl.take<int>((size_t)B * gprx::LB_NI), o_ri = dl.take<int>((size_t)B * 4);
+  const size_t oh_res = hl.take<double>(rd), oh_act = hl.take<int>(B), oh_ri = hl.take<int>((size_t)B * 4);
+  DevBlock dbuf = dev_block(dl.size);
+  if (!dbuf) return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: workspace");
+  PinBlock hbuf = pin_block(hl.size);
+  if (!hbuf) return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: host buffer");
+  a.ws = at<double>(dbuf.get(), o_ws);
+  double* th0d = at<double>(dbuf.get(), o_th0);
   a.theta0 = th0d;
-  a.result = th0d + (size_t)B * n;
-  a.iws = (int*)(a.result + rd);
+  a.result = at<double>(dbuf.get(), o_res);
+  a.iws = at<int>(dbuf.get(), o_iws);
   // the optimisers' activity flags double as the evaluation mask of the rounds (finished slots are
   // skipped by every kernel); a per-batch buffer, so the captured round graph is reused across calls
   a.active = b->opt_active;
-  a.result_i = a.iws + (size_t)B * gprx::LB_NI + B;
-  double* h_res = (double*)hbuf;
-  int* h_act = (int*)(h_res + rd);
-  int* h_ri = h_act + B;
+  a.result_i = at<int>(dbuf.get(), o_ri);
+  double* h_res = at<double>(hbuf.get(), oh_res);
+  int* h_act = at<int>(hbuf.get(), oh_act);
+  int* h_ri = at<int>(hbuf.get(), oh_ri);
   // theta, L and the factorisation flags are overwritten from here on: the batch holds no valid
   // factorisation until the refit below has succeeded for every slot
   b->factored = false;
@@ -1068,17 +1083,9 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
   const int trr = b->opt_trace ? b->opt_trace_rounds : 0;
   const size_t trs = (size_t)B * (2 * n + 1);  // staged doubles per round: theta(n), out(n + 1)
   std::vector<int> tr_act((size_t)trr * B, 0);
-  double* h_tr = nullptr;
-  if (trr > 0 && hipHostMalloc((void**)&h_tr, (size_t)trr * trs * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: trace buffer");
-  }
-  struct FreeTr {
-    double* h;
-    ~FreeTr() {
-      if (h) (void)hipHostFree(h);
-    }
-  } ftr{h_tr};
+  PinBlock trbuf = trr > 0 ? pin_block((size_t)trr * trs * sizeof(double)) : PinBlock();
+  if (trr > 0 && !trbuf) return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: trace buffer");
+  double* h_tr = (double*)trbuf.get();
   HIPCHK(c, hipMemcpyAsync(th0d, theta0, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   gprx::launch_lbfgs(a, db, 1, c->stream);
   db.active = a.active;
@@ -1227,6 +1234,48 @@ int gprx_gp_sample(gprx_gp* gp, const double* Xs, int M, const double* Z, int S,
   return gprx_batch_sample(gp->batch, Z, S, 0, samples, jitter, nullptr);
 }
 
+// ---- physics calls: common parts ----------------------------------------------------------------
+// device scratch of a context for the physics calls: [args | in | out], grown on demand
+static int ctx_scratch(gprx_ctx* c, size_t need, char** base) {
+  if (need > c->rcap) {
+    if (c->rbuf) HIPCHK(c, hipFree(c->rbuf));
+    c->rbuf = nullptr;
+    c->rcap = 0;
+    HIPCHK(c, hipMalloc(&c->rbuf, need));
+    c->rcap = need;
+  }
+  *base = (char*)c->rbuf;
+  return GPRX_OK;
+}
+
+// The ngroups x G GPs of a rollout (entry point fn), gathered from batch slots of this context that
+// have input dimension d (dwhat: how the message names it), are factorised and passed their last
+// evaluation; the trajectories' groups range-checked.  *np: the training points a trajectory step
+// visits, summed over the trajectories (the launch's flop and byte estimates).
+static int rollout_gps(gprx_ctx* c, const std::string& fn, int ngroups, int G, gprx_batch* const* batches, const int* slots,
+                       int d, const std::string& dwhat, int T, const int* traj_group, std::vector<gprx::RolloutGP>& gps,
+                       double* np) {
+  gps.resize((size_t)ngroups * G);
+  for (size_t k = 0; k < gps.size(); ++k) {
+    gprx_batch* b = batches[k];
+    const int s = slots[k];
+    if (!b || b->ctx != c || s < 0 || s >= b->db.B)
+      return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": GP " + std::to_string(k) + " is not a slot of a batch of this context");
+    if (b->db.d != d)
+      return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": input dimension " + std::to_string(b->db.d) + " != " + dwhat);
+    if (!b->factored) return set_err(c, GPRX_NOT_READY, fn + ": batch not factorised (run it first)");
+    if (b->h_status[s] != 0) return set_err(c, b->h_status[s], fn + ": slot " + std::to_string(s) + " failed its last evaluation");
+    const DevBatch& db = b->db;
+    gps[k] = gprx::RolloutGP{db.X + (size_t)s * db.Npad * db.d, db.alpha + (size_t)s * db.Npad, db.params + (size_t)s * db.pst, db.N, 0};
+  }
+  *np = 0.0;
+  for (int t = 0; t < T; ++t) {
+    if (traj_group[t] < 0 || traj_group[t] >= ngroups) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": trajectory group out of range");
+    for (int g = 0; g < G; ++g) *np += gps[(size_t)traj_group[t] * G + g].N;
+  }
+  return GPRX_OK;
+}
+
 // ---- rollout in minimal coordinates ------------------------------------------------------------
 int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, int ngroups,
                      gprx_batch* const* batches, const int* slots, int T, const int* traj_group,
@@ -1243,43 +1292,27 @@ int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, in
   const int ang0 = mech == GPRX_MECH_CP ? 0 : 1, ang1 = nc > 1 ? 1 : 0;
   const int dobs = (usesin && ang0 ? 3 : 2) + (nc > 1 ? (usesin && ang1 ? 3 : 2) : 0);
   std::lock_guard<std::mutex> g(c->mu);
-  std::vector<gprx::RolloutGP> gps((size_t)ngroups * nc);
-  for (size_t k = 0; k < gps.size(); ++k) {
-    gprx_batch* b = batches[k];
-    const int s = slots[k];
-    if (!b || b->ctx != c || s < 0 || s >= b->db.B)
-      return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min: GP " + std::to_string(k) + " is not a slot of a batch of this context");
-    if (b->db.d != dobs)
-      return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min: input dimension " + std::to_string(b->db.d) + " != " + std::to_string(dobs) + " for this mechanism / usesin");
-    if (!b->factored) return set_err(c, GPRX_NOT_READY, "gprx_rollout_min: batch not factorised (run it first)");
-    if (b->h_status[s] != 0) return set_err(c, b->h_status[s], "gprx_rollout_min: slot " + std::to_string(s) + " failed its last evaluation");
-    const DevBatch& db = b->db;
-    gps[k] = gprx::RolloutGP{db.X + (size_t)s * db.Npad * db.d, db.alpha + (size_t)s * db.Npad, db.params + (size_t)s * db.pst, db.N, 0};
-  }
-  for (int t = 0; t < T; ++t)
-    if (traj_group[t] < 0 || traj_group[t] >= ngroups) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min: trajectory group out of range");
+  std::vector<gprx::RolloutGP> gps;
+  double np = 0.0;
+  int rc = rollout_gps(c, "gprx_rollout_min", ngroups, nc, batches, slots, dobs,
+                       std::to_string(dobs) + " for this mechanism / usesin", T, traj_group, gps, &np);
+  if (rc) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   // one device buffer: [gps | group | start | out]
-  const size_t o_grp = gps.size() * sizeof(gprx::RolloutGP);
-  const size_t o_st = (o_grp + (size_t)T * sizeof(int) + 15) / 16 * 16;
-  const size_t o_out = o_st + (size_t)T * 2 * nc * sizeof(double);
-  const size_t need = o_out + (size_t)T * 2 * nc * sizeof(double);
-  if (need > c->rcap) {
-    if (c->rbuf) HIPCHK(c, hipFree(c->rbuf));
-    c->rbuf = nullptr;
-    c->rcap = 0;
-    HIPCHK(c, hipMalloc(&c->rbuf, need));
-    c->rcap = need;
-  }
-  char* base = (char*)c->rbuf;
-  HIPCHK(c, hipMemcpyAsync(base, gps.data(), o_grp, hipMemcpyHostToDevice, c->stream));
+  const size_t sw = (size_t)T * 2 * nc * sizeof(double);
+  Layout l;
+  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
+               o_out = l.take<char>(sw);
+  char* base;
+  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
+  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_st, start, (size_t)T * 2 * nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
   gprx::RolloutArgs a{};
-  a.gps = (const gprx::RolloutGP*)base;
-  a.group = (const int*)(base + o_grp);
-  a.start = (const double*)(base + o_st);
-  a.out = (double*)(base + o_out);
+  a.gps = at<gprx::RolloutGP>(base, o_gps);
+  a.group = at<int>(base, o_grp);
+  a.start = at<double>(base, o_st);
+  a.out = at<double>(base, o_out);
   a.T = T;
   a.nc = nc;
   a.d = dobs;
@@ -1288,13 +1321,10 @@ int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, in
   a.ang0 = ang0;
   a.ang1 = ang1;
   a.dt = dt;
-  double np = 0.0;
-  for (int t = 0; t < T; ++t)
-    for (int q = 0; q < nc; ++q) np += gps[(size_t)traj_group[t] * nc + q].N;
   timed(c, c->stream, "rollout", np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0,
         [&] { gprx::launch_rollout(a, c->dist_mode, c->stream); });
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, (size_t)T * 2 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
   return GPRX_OK;
@@ -1393,103 +1423,72 @@ static bool build_mech(int mech, gprx::MechDev& M) {
   return 6 * M.nb + M.nd <= gprx::PJ_MAXN;
 }
 
-// device scratch of a context for the physics calls: [args | in | out], grown on demand
-static int ctx_scratch(gprx_ctx* c, size_t need, char** base) {
-  if (need > c->rcap) {
-    if (c->rbuf) HIPCHK(c, hipFree(c->rbuf));
-    c->rbuf = nullptr;
-    c->rcap = 0;
-    HIPCHK(c, hipMalloc(&c->rbuf, need));
-    c->rcap = need;
-  }
-  *base = (char*)c->rbuf;
-  return GPRX_OK;
-}
-static size_t al16(size_t x) { return (x + 15) / 16 * 16; }
+}  // extern "C"
 
-int gprx_projectv(gprx_ctx* c, int mech, double dt, int T, const double* cstates, const double* vw_pred,
-                  double regularizer, int newton_iter, double eps, double* vw_out, int* iterations, int* status) {
+namespace {
+
+// gprx_projectv and gprx_vi_step (name, without the prefix): per trajectory a CState of 13 nb
+// doubles and, when in2_w > 0, a second input of in2_w nb doubles go in; out_w nb doubles, the
+// Newton iterations and a status come out, the latter two only where the caller wants them.  Args
+// is the launcher's argument struct; `extra` sets the fields the two do not share.
+template <class Args, class Extra>
+int newton_call(gprx_ctx* c, const char* name, int mech, double dt, int T, const double* cstates, const double* in2, int in2_w,
+                double regularizer, int newton_iter, double eps, double* out, int out_w, int* iterations, int* status,
+                void (*launch)(const Args&, hipStream_t), Extra extra) {
   if (!c) return GPRX_INVALID_ARGUMENT;
-  gprx::MechDev M;
-  if (!build_mech(mech, M) || T < 0 || newton_iter < 0 || !(dt > 0.0) || !std::isfinite(regularizer) || !(eps >= 0.0))
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_projectv: bad mechanism / T / newton_iter / dt / regularizer / eps");
+  const std::string fn = std::string("gprx_") + name;
+  Args a{};
+  if (!build_mech(mech, a.mech) || T < 0 || newton_iter < 0 || !(dt > 0.0) || !std::isfinite(regularizer) || !(eps >= 0.0))
+    return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / T / newton_iter / dt / regularizer / eps");
   if (T == 0) return GPRX_OK;
-  if (!cstates || !vw_pred || !vw_out) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_projectv: null argument");
+  if (!cstates || (in2_w > 0 && !in2) || !out) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
   std::lock_guard<std::mutex> g(c->mu);
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  const int nb = M.nb;
-  const size_t o_cs = 0, o_vw = al16(o_cs + (size_t)T * 13 * nb * 8), o_out = al16(o_vw + (size_t)T * 6 * nb * 8),
-               o_it = al16(o_out + (size_t)T * 6 * nb * 8), o_st = al16(o_it + (size_t)T * 4), need = al16(o_st + (size_t)T * 4);
+  const size_t nb = a.mech.nb, n_cs = (size_t)T * 13 * nb, n_in2 = (size_t)T * in2_w * nb, n_out = (size_t)T * out_w * nb;
+  Layout l;
+  const size_t o_cs = l.take<double>(n_cs), o_in2 = l.take<double>(n_in2), o_out = l.take<double>(n_out),
+               o_it = l.take<int>(T), o_st = l.take<int>(T);
   char* base;
-  int rc = ctx_scratch(c, need, &base);
+  int rc = ctx_scratch(c, l.size, &base);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(base + o_cs, cstates, (size_t)T * 13 * nb * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_vw, vw_pred, (size_t)T * 6 * nb * 8, hipMemcpyHostToDevice, c->stream));
-  gprx::ProjArgs a{};
-  a.mech = M;
+  HIPCHK(c, hipMemcpyAsync(base + o_cs, cstates, n_cs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (in2_w > 0) HIPCHK(c, hipMemcpyAsync(base + o_in2, in2, n_in2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   a.dt = dt;
   a.reg = regularizer;
   a.eps = eps;
   a.iters = newton_iter;
   a.T = T;
-  a.cs = (const double*)(base + o_cs);
-  a.vw = (const double*)(base + o_vw);
-  a.out = (double*)(base + o_out);
-  a.iters_out = (int*)(base + o_it);
-  a.status = (int*)(base + o_st);
-  timed(c, c->stream, "projectv", 0.0, (double)T * 8.0 * (13 + 12) * nb, [&] { gprx::launch_project(a, c->stream); });
+  a.cs = at<double>(base, o_cs);
+  a.out = at<double>(base, o_out);
+  a.iters_out = at<int>(base, o_it);
+  a.status = at<int>(base, o_st);
+  extra(a, at<double>(base, o_in2));
+  timed(c, c->stream, name, 0.0, (double)T * 8.0 * (13 + in2_w + out_w) * nb, [&] { launch(a, c->stream); });
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(vw_out, base + o_out, (size_t)T * 6 * nb * 8, hipMemcpyDeviceToHost, c->stream));
-  std::vector<int> it(T), st(T);
-  HIPCHK(c, hipMemcpyAsync(it.data(), base + o_it, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(st.data(), base + o_st, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, base + o_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (iterations) HIPCHK(c, hipMemcpyAsync(iterations, base + o_it, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_st, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  if (iterations) memcpy(iterations, it.data(), (size_t)T * 4);
-  if (status) memcpy(status, st.data(), (size_t)T * 4);
   return GPRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gprx_projectv(gprx_ctx* c, int mech, double dt, int T, const double* cstates, const double* vw_pred,
+                  double regularizer, int newton_iter, double eps, double* vw_out, int* iterations, int* status) {
+  return newton_call<gprx::ProjArgs>(c, "projectv", mech, dt, T, cstates, vw_pred, 6, regularizer, newton_iter, eps, vw_out, 6,
+                                     iterations, status, gprx::launch_project,
+                                     [](gprx::ProjArgs& a, const double* vw) { a.vw = vw; });
 }
 
 int gprx_vi_step(gprx_ctx* c, int mech, double dt, int T, const double* cstates, double regularizer, int newton_iter,
                  double eps, double* out, int* iterations, int* status) {
-  if (!c) return GPRX_INVALID_ARGUMENT;
-  gprx::MechDev M;
-  if (!build_mech(mech, M) || T < 0 || newton_iter < 0 || !(dt > 0.0) || !std::isfinite(regularizer) || !(eps >= 0.0))
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_vi_step: bad mechanism / T / newton_iter / dt / regularizer / eps");
-  if (T == 0) return GPRX_OK;
-  if (!cstates || !out) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_vi_step: null argument");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  const int nb = M.nb;
-  const size_t o_cs = 0, o_out = al16(o_cs + (size_t)T * 13 * nb * 8), o_it = al16(o_out + (size_t)T * 13 * nb * 8),
-               o_st = al16(o_it + (size_t)T * 4), need = al16(o_st + (size_t)T * 4);
-  char* base;
-  int rc = ctx_scratch(c, need, &base);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(base + o_cs, cstates, (size_t)T * 13 * nb * 8, hipMemcpyHostToDevice, c->stream));
-  gprx::ViArgs a{};
-  a.mech = M;
-  a.dt = dt;
-  a.reg = regularizer;
-  a.eps = eps;
-  a.grav = 9.81;  // |mechanism.g| (simulations.jl; gprx/vi.py GRAV)
-  a.iters = newton_iter;
-  a.T = T;
-  a.cs = (const double*)(base + o_cs);
-  a.out = (double*)(base + o_out);
-  a.iters_out = (int*)(base + o_it);
-  a.status = (int*)(base + o_st);
-  timed(c, c->stream, "vi_step", 0.0, (double)T * 8.0 * 26 * nb, [&] { gprx::launch_vi_step(a, c->stream); });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, base + o_out, (size_t)T * 13 * nb * 8, hipMemcpyDeviceToHost, c->stream));
-  std::vector<int> it(T), st(T);
-  HIPCHK(c, hipMemcpyAsync(it.data(), base + o_it, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(st.data(), base + o_st, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  collect(c);
-  if (iterations) memcpy(iterations, it.data(), (size_t)T * 4);
-  if (status) memcpy(status, st.data(), (size_t)T * 4);
-  return GPRX_OK;
+  return newton_call<gprx::ViArgs>(c, "vi_step", mech, dt, T, cstates, nullptr, 0, regularizer, newton_iter, eps, out, 13,
+                                   iterations, status, gprx::launch_vi_step,
+                                   [](gprx::ViArgs& a, const double*) { a.grav = 9.81; });  // |mechanism.g| (simulations.jl; gprx/vi.py GRAV)
 }
 
 int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups,
@@ -1513,31 +1512,20 @@ int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regular
     a.vw[g] = vw_idx1[g] - 1;
   }
   std::lock_guard<std::mutex> lk(c->mu);
-  std::vector<gprx::RolloutGP> gps((size_t)ngroups * G);
-  for (size_t k = 0; k < gps.size(); ++k) {
-    gprx_batch* b = batches[k];
-    const int s = slots[k];
-    if (!b || b->ctx != c || s < 0 || s >= b->db.B)
-      return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: GP " + std::to_string(k) + " is not a slot of a batch of this context");
-    if (b->db.d != d)
-      return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: input dimension " + std::to_string(b->db.d) + " != 13 nbodies");
-    if (!b->factored) return set_err(c, GPRX_NOT_READY, "gprx_rollout_max: batch not factorised (run it first)");
-    if (b->h_status[s] != 0) return set_err(c, b->h_status[s], "gprx_rollout_max: slot " + std::to_string(s) + " failed its last evaluation");
-    const DevBatch& db = b->db;
-    gps[k] = gprx::RolloutGP{db.X + (size_t)s * db.Npad * db.d, db.alpha + (size_t)s * db.Npad, db.params + (size_t)s * db.pst, db.N, 0};
-  }
-  for (int t = 0; t < T; ++t)
-    if (traj_group[t] < 0 || traj_group[t] >= ngroups) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: trajectory group out of range");
-  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  const size_t o_grp = al16(gps.size() * sizeof(gprx::RolloutGP)), o_st = al16(o_grp + (size_t)T * 4),
-               o_out = al16(o_st + (size_t)T * d * 8), o_pe = al16(o_out + (size_t)T * d * 8),
-               o_ss = al16(o_pe + (size_t)T * 8), need = al16(o_ss + (size_t)T * 4);
-  char* base;
-  int rc = ctx_scratch(c, need, &base);
+  std::vector<gprx::RolloutGP> gps;
+  double np = 0.0;
+  int rc = rollout_gps(c, "gprx_rollout_max", ngroups, G, batches, slots, d, "13 nbodies", T, traj_group, gps, &np);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(base, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_st, start, (size_t)T * d * 8, hipMemcpyHostToDevice, c->stream));
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const size_t sw = (size_t)T * d * sizeof(double);
+  Layout l;
+  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
+               o_out = l.take<char>(sw), o_pe = l.take<double>(T), o_ss = l.take<int>(T);
+  char* base;
+  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
+  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
   a.mech = M;
   a.dt = dt;
   a.reg = regularizer;
@@ -1547,27 +1535,20 @@ int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regular
   a.T = T;
   a.G = G;
   a.d = d;
-  a.gps = (const gprx::RolloutGP*)base;
-  a.group = (const int*)(base + o_grp);
-  a.start = (const double*)(base + o_st);
-  a.out = (double*)(base + o_out);
-  a.perr = (double*)(base + o_pe);
-  a.status = (int*)(base + o_ss);
-  double np = 0.0;
-  for (int t = 0; t < T; ++t)
-    for (int g = 0; g < G; ++g) np += gps[(size_t)traj_group[t] * G + g].N;
+  a.gps = at<gprx::RolloutGP>(base, o_gps);
+  a.group = at<int>(base, o_grp);
+  a.start = at<double>(base, o_st);
+  a.out = at<double>(base, o_out);
+  a.perr = at<double>(base, o_pe);
+  a.status = at<int>(base, o_ss);
   timed(c, c->stream, "rollout_max", np * steps * (3.0 * d + 24.0), np * steps * (d + 1) * 8.0,
         [&] { gprx::launch_rollout_max(a, c->dist_mode, c->stream); });
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, (size_t)T * d * 8, hipMemcpyDeviceToHost, c->stream));
-  std::vector<double> pe(T);
-  std::vector<int> ss(T);
-  HIPCHK(c, hipMemcpyAsync(pe.data(), base + o_pe, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(ss.data(), base + o_ss, (size_t)T * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
+  if (proj_err) HIPCHK(c, hipMemcpyAsync(proj_err, base + o_pe, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_ss, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  if (proj_err) memcpy(proj_err, pe.data(), (size_t)T * 8);
-  if (status) memcpy(status, ss.data(), (size_t)T * 4);
   return GPRX_OK;
 }
 

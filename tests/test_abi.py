@@ -182,6 +182,25 @@ def test_batch_bytes_and_the_addressing_guard():
     assert L.lib.gprx_batch_bytes(1, 1, 1, 0, None) == L.INVALID_ARGUMENT
 
 
+def test_batch_bytes_exact_values():
+    """gprx_batch_bytes to the byte, for (B, d, N, M_max) with even and odd d (the d | 1 stride of
+    the centred inputs), one tile, and sizes that are no multiple of 64.  The numbers were recorded
+    from the library before its buffers were described in one list per group: the lists must
+    account for exactly what the hand-written expressions did."""
+    recorded = {
+        (1, 1, 1, 0): 203084,
+        (1, 2, 64, 64): 205164,
+        (2, 4, 65, 129): 1768104,
+        (3, 13, 130, 16): 4914300,
+        (8, 26, 2048, 100): 1375693728,
+        (3, 52, 4096, 0): 2043766044,
+        (240, 26, 2048, 100): 41270444352,
+        (1, 64, 1000, 1025): 53076628,
+    }
+    for shape, want in recorded.items():
+        assert _bytes(*shape) == (0, want), shape
+
+
 def test_opt_trace_capacity_is_checked_without_a_batch():
     """gprx_batch_set_opt_trace(NULL, ...) is an argument error (the capacity check itself needs a
     batch: tests/test_gpu.py::test_opt_trace_capacity_checked)."""

@@ -673,6 +673,101 @@ def test_batch_bytes_match_the_allocation(gprx, ctx):
         assert abs(used - want) <= 0.01 * want + (64 << 20), (B, d, N, M, used, want)
 
 
+def _capacity(b):
+    import ctypes as C
+
+    from gprx import _lib as L
+
+    m = C.c_int()
+    L.check(L.lib.gprx_batch_dims(b.h, None, None, None, C.byref(m)))
+    return m.value
+
+
+def test_regrown_test_buffers_give_a_fresh_batch_s_results(gprx, ctx, golden_dir):
+    """gprx_batch_set_test past the capacity frees and re-allocates the test buffers, and the next
+    gprx_batch_predict_cov re-allocates its workspace for the new capacity: a batch created for 0
+    test points (capacity 64) that predicts at 5 and then at 70 points (capacity 128) answers bit
+    for bit as a batch created for 70, in the mean, the variance and the joint covariance."""
+    z = np.load(golden_dir / "p2_n256.npz")
+    X, Y, th, Xs = z["X"], z["Y"], z["theta"], z["Xs"]
+    G = Y.shape[0]
+    T = np.tile(th, (G, 1))
+    assert Xs.shape[1] >= 5
+    Xs70 = np.tile(Xs, (1, -(-70 // Xs.shape[1])))[:, :70]
+
+    fresh = gprx.GPBatch(G, X.shape[0], X.shape[1], 70, ctx=ctx)
+    fresh.set_train(X, Y)
+    fresh.set_test(Xs70)
+    assert np.all(fresh.run(T, grad=False)["status"] == 0)
+    mu_f, var_f = fresh.predict()
+    muc_f, cov_f = fresh.predict_cov()
+    fresh.close()
+    np.testing.assert_array_equal(muc_f, mu_f)
+
+    b = gprx.GPBatch(G, X.shape[0], X.shape[1], 0, ctx=ctx)
+    assert _capacity(b) == 64
+    b.set_train(X, Y)
+    assert np.all(b.run(T, grad=False)["status"] == 0)
+    b.set_test(Xs70[:, :5])
+    mu5, var5 = b.predict()
+    muc5, _ = b.predict_cov()  # a workspace for capacity 64 exists before the regrow
+    assert _capacity(b) == 64
+    b.set_test(Xs70)
+    assert _capacity(b) == 128
+    mu70, var70 = b.predict()
+    muc70, cov70 = b.predict_cov()
+    b.close()
+    np.testing.assert_array_equal(mu5, mu_f[:, :5])
+    np.testing.assert_array_equal(var5, var_f[:, :5])
+    np.testing.assert_array_equal(muc5, mu5)
+    np.testing.assert_array_equal(mu70, mu_f)
+    np.testing.assert_array_equal(var70, var_f)
+    np.testing.assert_array_equal(muc70, mu70)
+    np.testing.assert_array_equal(cov70, cov_f)
+
+
+def test_regrow_and_covariance_workspace_match_their_byte_counts(gprx, ctx):
+    """Device memory in use (hipMemGetInfo, as test_batch_bytes_match_the_allocation reads it, and
+    to its tolerance of 1 % + 64 MiB for the allocator's rounding) follows the library's own
+    accounting through a batch's life: growing the test capacity from 64 to 2048 points takes the
+    difference of gprx_batch_bytes, the first gprx_batch_predict_cov takes gprx_batch_cov_bytes
+    (1.3 GB here: a buffer missing from or doubled in either would show), and closing the batch
+    gives everything back."""
+    import ctypes as C
+
+    from gprx import _lib as L, data, shard
+
+    def free():
+        f, t = C.c_uint64(), C.c_uint64()
+        L.check(L.lib.gprx_ctx_mem_info(ctx.h, C.byref(f), C.byref(t)))
+        assert 0 < f.value <= t.value
+        return f.value
+
+    def close_to(used, want):
+        print("device bytes used", used, "accounted", want)
+        return abs(used - want) <= 0.01 * want + (64 << 20)
+
+    B, d, N = 8, 26, 2048
+    tr = data.make_trial("P2", N, 64, seed=data.trial_seed("P2", 0))
+    th = data.theta0("P2", N)
+    cov_want = C.c_uint64()
+    L.check(L.lib.gprx_batch_cov_bytes(B, N, N, C.byref(cov_want)))
+    assert cov_want.value > 1.3e9
+    f0 = free()
+    b = gprx.GPBatch(B, d, N, 64, ctx=ctx)
+    b.set_train(tr["X"], np.tile(tr["Y"][0], (B, 1)))
+    f1 = free()
+    b.set_test(tr["X"])  # N test points: the training inputs
+    f2 = free()
+    assert close_to(f1 - f2, shard.batch_bytes(B, d, N, N) - shard.batch_bytes(B, d, N, 64))
+    assert np.all(b.run(np.tile(th, (B, 1)), grad=False)["status"] == 0)
+    b.predict_cov()
+    f3 = free()
+    assert close_to(f2 - f3, cov_want.value)
+    b.close()
+    assert close_to(f0 - free(), 0)
+
+
 def test_opt_trace_capacity_checked(gprx, ctx, golden_dir):
     """gprx_batch_set_opt_trace refuses a buffer smaller than max_rounds * B * (2(d+2)+2) doubles
     (the write size was implied) and registers one that is large enough."""

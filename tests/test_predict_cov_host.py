@@ -55,6 +55,24 @@ def test_cov_bytes_arithmetic():
         assert v == 8 * B * (Np * Mp + 2 * Mp * Mp) + 8 * B * 2 * Mp * Mp + 12 * B
 
 
+def test_cov_bytes_exact_values():
+    """gprx_batch_cov_bytes to the byte for (B, N, M_max), recorded from the library before the
+    workspace's buffers were described in one list (tests/test_abi.py
+    test_batch_bytes_exact_values: the same shapes, without d)."""
+    recorded = {
+        (1, 1, 0): 163852,
+        (1, 64, 64): 163852,
+        (2, 65, 129): 2752536,
+        (3, 130, 16): 688164,
+        (8, 2048, 100): 20971616,
+        (3, 4096, 0): 6684708,
+        (240, 2048, 100): 629148480,
+        (1, 1000, 1025): 46792716,
+    }
+    for shape, want in recorded.items():
+        assert cov_bytes(*shape) == (L.OK, want), shape
+
+
 def test_cov_bytes_monotone():
     base = cov_bytes(4, 200, 100)[1]
     assert cov_bytes(5, 200, 100)[1] > base
