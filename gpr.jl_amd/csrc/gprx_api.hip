@@ -1491,36 +1491,39 @@ int gprx_vi_step(gprx_ctx* c, int mech, double dt, int T, const double* cstates,
                                    [](gprx::ViArgs& a, const double*) { a.grav = 9.81; });  // |mechanism.g| (simulations.jl; gprx/vi.py GRAV)
 }
 
-int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups,
-                     gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1, int T,
-                     const int* traj_group, const double* start, double* final_state, double* proj_err, int* status) {
+// gprx_rollout_max (vi_regularizer null: MeanZero GPs, k_rollout_max) and gprx_rollout_max_md (the
+// physics mean per step, k_rollout_max<., RolloutMaxMdArgs>): one validation, scratch layout and launch
+static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat, int mech, double dt, int steps, double regularizer,
+                            const double* vi_regularizer, int ngroups, gprx_batch* const* batches, const int* slots, int G,
+                            const int* vw_idx1, int T, const int* traj_group, const double* start, double* final_state,
+                            double* proj_err, int* status, int* vi_status) {
   if (!c) return GPRX_INVALID_ARGUMENT;
   gprx::MechDev M;
   if (!build_mech(mech, M) || steps < 0 || ngroups < 1 || T < 0 || G < 1 || G > gprx::PJ_MAXG || !(dt > 0.0) ||
-      !std::isfinite(regularizer))
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: bad mechanism / steps / groups / G / dt / regularizer");
+      !std::isfinite(regularizer) || (vi_regularizer && !std::isfinite(*vi_regularizer)))
+    return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / steps / groups / G / dt / regularizer");
   if (T == 0) return GPRX_OK;
   if (!batches || !slots || !vw_idx1 || !traj_group || !start || !final_state)
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: null argument");
+    return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
   const int d = 13 * M.nb;
-  gprx::RolloutMaxArgs a{};
+  gprx::RolloutMaxMdArgs a{};
   for (int g = 0; g < G; ++g) {
     const int k = (vw_idx1[g] - 1) % 13;
     if (vw_idx1[g] < 1 || vw_idx1[g] > d || k < 7)
-      return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_max: vw index " + std::to_string(vw_idx1[g]) +
+      return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": vw index " + std::to_string(vw_idx1[g]) +
                                                    " is not a velocity / angular-velocity slot of the CState");
     a.vw[g] = vw_idx1[g] - 1;
   }
   std::lock_guard<std::mutex> lk(c->mu);
   std::vector<gprx::RolloutGP> gps;
   double np = 0.0;
-  int rc = rollout_gps(c, "gprx_rollout_max", ngroups, G, batches, slots, d, "13 nbodies", T, traj_group, gps, &np);
+  int rc = rollout_gps(c, fn, ngroups, G, batches, slots, d, "13 nbodies", T, traj_group, gps, &np);
   if (rc) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   const size_t sw = (size_t)T * d * sizeof(double);
   Layout l;
   const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
-               o_out = l.take<char>(sw), o_pe = l.take<double>(T), o_ss = l.take<int>(T);
+               o_out = l.take<char>(sw), o_pe = l.take<double>(T), o_ss = l.take<int>(T), o_vs = l.take<int>(T);
   char* base;
   if ((rc = ctx_scratch(c, l.size, &base))) return rc;
   HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
@@ -1541,12 +1544,95 @@ int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regular
   a.out = at<double>(base, o_out);
   a.perr = at<double>(base, o_pe);
   a.status = at<int>(base, o_ss);
-  timed(c, c->stream, "rollout_max", np * steps * (3.0 * d + 24.0), np * steps * (d + 1) * 8.0,
-        [&] { gprx::launch_rollout_max(a, c->dist_mode, c->stream); });
+  if (vi_regularizer)  // newton! as gprx_vi_step's callers run it (gprx/projection.py vi_step)
+    a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? at<int>(base, o_vs) : nullptr};
+  timed(c, c->stream, stat, np * steps * (3.0 * d + 24.0), np * steps * (d + 1) * 8.0, [&] {
+    if (vi_regularizer) gprx::launch_rollout_max_md(a, c->dist_mode, c->stream);
+    else gprx::launch_rollout_max(a, c->dist_mode, c->stream);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
   if (proj_err) HIPCHK(c, hipMemcpyAsync(proj_err, base + o_pe, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_ss, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (vi_regularizer && vi_status)
+    HIPCHK(c, hipMemcpyAsync(vi_status, base + o_vs, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  return GPRX_OK;
+}
+
+int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups,
+                     gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1, int T,
+                     const int* traj_group, const double* start, double* final_state, double* proj_err, int* status) {
+  return rollout_max_call(c, "gprx_rollout_max", "rollout_max", mech, dt, steps, regularizer, nullptr, ngroups, batches, slots, G,
+                          vw_idx1, T, traj_group, start, final_state, proj_err, status, nullptr);
+}
+
+int gprx_rollout_max_md(gprx_ctx* c, int mech, double dt, int steps, double regularizer, double vi_regularizer, int ngroups,
+                        gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1, int T,
+                        const int* traj_group, const double* start, double* final_state, double* proj_err, int* status,
+                        int* vi_status) {
+  return rollout_max_call(c, "gprx_rollout_max_md", "rollout_max_md", mech, dt, steps, regularizer, &vi_regularizer, ngroups,
+                          batches, slots, G, vw_idx1, T, traj_group, start, final_state, proj_err, status, vi_status);
+}
+
+// predictdynamicsmin with MeanDynamics GPs (examples/utils/predictdynamics.jl:30-102 with
+// src/mDynamics.jl:41-55): gprx_rollout_min's validation and layout, plus the physics step
+int gprx_rollout_min_md(gprx_ctx* c, int mech, int usesin, double dt, int steps, double vi_regularizer, int ngroups,
+                        gprx_batch* const* batches, const int* slots, int T, const int* traj_group, const double* start,
+                        double* final_state, int* status, int* vi_status) {
+  if (!c) return GPRX_INVALID_ARGUMENT;
+  gprx::RolloutMinMdArgs a{};
+  if (!build_mech(mech, a.mech) || steps < 0 || ngroups < 1 || T < 0 || !(dt > 0.0) || !std::isfinite(dt) ||
+      !std::isfinite(vi_regularizer))
+    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min_md: bad mechanism / steps / groups / dt / regularizer");
+  if (T == 0) return GPRX_OK;
+  if (!batches || !slots || !traj_group || !start || !final_state)
+    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min_md: null argument");
+  const int nc = mech == GPRX_MECH_P1 ? 1 : 2;  // coordinates and features as gprx_rollout_min
+  const int ang0 = mech == GPRX_MECH_CP ? 0 : 1, ang1 = nc > 1 ? 1 : 0;
+  const int dobs = (usesin && ang0 ? 3 : 2) + (nc > 1 ? (usesin && ang1 ? 3 : 2) : 0);
+  std::lock_guard<std::mutex> g(c->mu);
+  std::vector<gprx::RolloutGP> gps;
+  double np = 0.0;
+  int rc = rollout_gps(c, "gprx_rollout_min_md", ngroups, nc, batches, slots, dobs,
+                       std::to_string(dobs) + " for this mechanism / usesin", T, traj_group, gps, &np);
+  if (rc) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  // one device buffer: [gps | group | start | out | status | vi_status]
+  const size_t sw = (size_t)T * 2 * nc * sizeof(double);
+  Layout l;
+  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
+               o_out = l.take<char>(sw), o_ss = l.take<int>(T), o_vs = l.take<int>(T);
+  char* base;
+  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
+  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
+  a.gps = at<gprx::RolloutGP>(base, o_gps);
+  a.group = at<int>(base, o_grp);
+  a.start = at<double>(base, o_st);
+  a.out = at<double>(base, o_out);
+  a.status = at<int>(base, o_ss);
+  a.T = T;
+  a.nc = nc;
+  a.d = dobs;
+  a.steps = steps;
+  a.mech_id = mech;
+  a.usesin = usesin ? 1 : 0;
+  a.ang0 = ang0;
+  a.ang1 = ang1;
+  a.dt = dt;
+  // link lengths of the experiment mechanisms (examples/utils/simulations.jl; gprx/rollout.py LENGTHS)
+  a.len[0] = mech == GPRX_MECH_CP ? 0.5 : 1.0;
+  a.len[1] = 1.0;
+  a.vi = gprx::RolloutViArgs{vi_regularizer, 1e-10, 9.81, 100, vi_status ? at<int>(base, o_vs) : nullptr};
+  timed(c, c->stream, "rollout_min_md", np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0,
+        [&] { gprx::launch_rollout_min_md(a, c->dist_mode, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_ss, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (vi_status) HIPCHK(c, hipMemcpyAsync(vi_status, base + o_vs, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
   return GPRX_OK;

@@ -159,7 +159,32 @@ struct RolloutMaxArgs {
   const double* start;  // T x d
   double* out;          // T x d final CStates
   double* perr;         // T mean projection error per step
-  int* status;          // T
+  int* status;          // T: 0 ok, 1 singular projection, 2 failed physics mean (MeanDynamics)
+};
+// MeanDynamics GPs (k_rollout_max_md, k_rollout_min_md): the variational-integrator step that gives
+// the prior mean at every step's state.  Kept apart from RolloutMaxArgs, so k_rollout_max's kernel
+// arguments are what they were.
+struct RolloutViArgs {
+  double reg, eps, grav;
+  int iters;
+  int* status;          // T or null: OR of the per-step physics statuses (ViArgs::status)
+};
+struct RolloutMaxMdArgs : RolloutMaxArgs {
+  RolloutViArgs vi;
+};
+// predictdynamicsmin with MeanDynamics GPs (k_rollout_min_md): RolloutArgs' rollout plus, per step,
+// the experiments' xtransform of the features into a CState and one variational-integrator step
+struct RolloutMinMdArgs {
+  MechDev mech;
+  const RolloutGP* gps;  // ngroups x nc
+  const int* group;      // T
+  const double* start;   // T x 2nc
+  double* out;           // T x 2nc: (q_cur, qdot_last) per coordinate (NaN row: failed physics mean)
+  int* status;           // T: 0 ok, 2 failed physics mean
+  int T, nc, d, steps, mech_id;
+  int usesin, ang0, ang1;
+  double dt, len[2];     // link lengths (gprx/rollout.py LENGTHS)
+  RolloutViArgs vi;
 };
 // One variational-integrator step (ConstrainedDynamics 0.7.4 newton!, restated in gprx/vi.py) for T
 // independent states: the MeanDynamics prior mean (src/mDynamics.jl:41-60).
@@ -176,6 +201,8 @@ struct ViArgs {
 void launch_project(const ProjArgs& a, hipStream_t s);
 void launch_vi_step(const ViArgs& a, hipStream_t s);
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s);
 
 // hyper-parameters -> kernel parameters for one slot, exactly as SEArd / GPE derive them:
 //   il2 = exp(-2 log ell), sf2 = exp(2 log sf), noise = exp(2 logNoise) + eps();

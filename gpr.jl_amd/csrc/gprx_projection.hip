@@ -19,6 +19,7 @@
 // current CState (the training points split over the workgroup), getvw, the projection (its LU
 // update over the whole workgroup), the projection error and updatestate!.
 #include "gprx_internal.h"
+#include <type_traits>
 
 namespace gprx {
 
@@ -569,6 +570,116 @@ __device__ __forceinline__ double vi_dyn_row(const PState& P, const MechDev& M, 
   for (int r = 0; r < nd; ++r) t += G[(size_t)r * n6 + j] * P.s[n6 + r];
   return d - t;
 }
+// [v]x (i, j) and v[i] by selects: a register array indexed by a lane-dependent value would live in
+// scratch memory
+__device__ __forceinline__ double sel3(const double* v, int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : v[2]); }
+__device__ __forceinline__ double skew_at(const double* v, int i, int j) {
+  if (i == j) return 0.0;
+  const double x = sel3(v, 3 - i - j);
+  return (j - i == 1 || j - i == -2) ? -x : x;
+}
+
+// The Newton solve of one variational-integrator step on NW waves (all NW * 64 threads call; P.xc /
+// qc / vc / wc and the discrete pose P.xk / qk set by set_states).  Leaves the solution (v2, w2 per
+// body, lambda) in P.s and returns the status: 0 converged, 1 not converged within iters, 2 failed
+// (a non-finite or singular system; P.s is then undefined); it: the iterations taken.  The Newton
+// matrix A (n x (n + 1)) and Gpos (nd x n6) live in dynamic LDS, pj_lds() onwards.
+// The whole workgroup runs it, as project<NW>: wave 0 builds the rows (one lane per sub-joint /
+// inertia entry / residual row), the zeroing, the -Gpos^T block and lu_solve's trailing update are
+// spread over every thread, and the finiteness test, the right-hand side, the substitutions and
+// the norms run redundantly on every wave from the same LDS values, so every wave takes the same
+// branch without a broadcast.  Each element sees the same operations in the same order for any
+// NW (k_vi_step's NW = 1 included).  Ends with a barrier: the caller may reuse the dynamic LDS.
+template <int NW>
+__device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double dt, double reg, double eps, double grav,
+                         int iters, int& it) {
+  constexpr int NT = 64 * NW;
+  const int tid = threadIdx.x & (NT - 1), l = tid & 63;
+  const bool w0 = tid < 64;
+  const int nb = M.nb, nd = M.nd, n6 = 6 * nb, n = n6 + nd, ldf = n + 1;
+  double* A = PJ_F;                         // the Newton matrix, rebuilt and factored each iteration
+  double* G = PJ_F + (size_t)n * ldf;       // Gpos (nd x n6), fixed
+  if (w0 && l < nb) {  // (sq1 I - [w1 x]) J w1; setsolution!: (v2, w2) start at the current velocities
+    const double* w1 = P.wc[l];
+    double Jw[3];
+    for (int i = 0; i < 3; ++i) Jw[i] = M.J[l][i][0] * w1[0] + M.J[l][i][1] * w1[1] + M.J[l][i][2] * w1[2];
+    const double sq1 = sqrt(4.0 / (dt * dt) - (w1[0] * w1[0] + w1[1] * w1[1] + w1[2] * w1[2]));
+    const double cr[3] = {w1[1] * Jw[2] - w1[2] * Jw[1], w1[2] * Jw[0] - w1[0] * Jw[2], w1[0] * Jw[1] - w1[1] * Jw[0]};
+    for (int i = 0; i < 3; ++i) {
+      mom1[l][i] = sq1 * Jw[i] - cr[i];
+      P.s[6 * l + i] = P.vc[l][i];
+      P.s[6 * l + 3 + i] = w1[i];
+    }
+  }
+  if (w0 && l >= n6 && l < n) P.s[l] = 0.0;
+  for (int i = tid; i < nd * n6; i += NT) G[i] = 0.0;
+  pj_sync<NW>();
+  if (w0 && l < M.nsub) subjoint_pose_jac(P, M.sub[l], n6, G);
+  pj_sync<NW>();
+  int status = 1;
+  it = 0;
+  for (int k = 1; k <= iters; ++k) {
+    // ---- the Newton matrix and the residual at the current solution
+    for (int i = tid; i < n * ldf; i += NT) A[i] = 0.0;
+    pj_sync<NW>();
+    if (w0) {
+      if (l < M.nsub) {
+        subjoint(P, M.sub[l], n6, ldf, dt, true, true, false);  // g(x3, q3) and dg/d(v2, w2)
+      } else if (l < M.nsub + 9 * nb) {  // d/dw2 [(sq2 I + [w2 x]) J w2] (gprx/vi.py)
+        const int e = l - M.nsub, b = e / 9, i = (e - 9 * b) / 3, kk = e - 9 * b - 3 * i;
+        const double* w2 = P.s + 6 * b + 3;
+        double Jw[3];
+        for (int q = 0; q < 3; ++q) Jw[q] = M.J[b][q][0] * w2[0] + M.J[b][q][1] * w2[1] + M.J[b][q][2] * w2[2];
+        const double sq2 = sqrt(4.0 / (dt * dt) - (w2[0] * w2[0] + w2[1] * w2[1] + w2[2] * w2[2]));
+        const double swJ = skew_at(w2, i, 0) * M.J[b][0][kk] + skew_at(w2, i, 1) * M.J[b][1][kk] + skew_at(w2, i, 2) * M.J[b][2][kk];
+        A[(6 * b + 3 + i) * ldf + 6 * b + 3 + kk] = ((sq2 * M.J[b][i][kk] + swJ) - skew_at(Jw, i, kk)) - sel3(Jw, i) * w2[kk] / sq2;
+      } else if (l < M.nsub + 12 * nb) {
+        const int e = l - M.nsub - 9 * nb, b = e / 3, c = e - 3 * b;
+        A[(6 * b + c) * ldf + 6 * b + c] = M.m[b] / dt;
+      }
+    }
+    for (int e = tid; e < n6 * nd; e += NT) {  // -Gpos^T (upper right), -reg I (lower right)
+      const int j = e / nd, r = e - j * nd;
+      A[j * ldf + n6 + r] = -G[(size_t)r * n6 + j];
+    }
+    if (w0 && l < nd && reg != 0.0) A[(n6 + l) * ldf + n6 + l] = -reg;
+    pj_sync<NW>();
+    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, grav, l);
+    pj_sync<NW>();
+    // a system that is not finite (|w| beyond 2/dt: the reference's sqrt throws a DomainError) or is
+    // singular (SingularException) fails the state.  Every wave scans the whole matrix.
+    bool fin = l < n ? isfinite(P.f[l]) : true;
+    for (int i = l; i < n * ldf; i += 64) fin = fin && isfinite(A[i]);
+    if (__any(!fin)) {
+      status = 2;
+      break;
+    }
+    double bvec = l < n ? P.f[l] : 0.0;
+    if (lu_solve<NW>(A, n, ldf, bvec) || __any(l < n && !isfinite(bvec))) {
+      status = 2;
+      break;
+    }
+    if (w0 && l < n) {
+      P.ds[l] = bvec;
+      P.s[l] = P.s[l] - bvec;
+    }
+    it = k;
+    pj_sync<NW>();
+    // ---- convergence: |f(s_new)| and |ds|
+    if (w0 && l < M.nsub) subjoint(P, M.sub[l], n6, ldf, dt, true, false, false);
+    pj_sync<NW>();
+    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, grav, l);
+    pj_sync<NW>();
+    const double fv = l < n ? P.f[l] : 0.0, dv = l < n ? P.ds[l] : 0.0;
+    const double nf = sqrt(wsum(fv * fv)), nds = sqrt(wsum(dv * dv));
+    if (nf < eps && nds < eps) {
+      status = 0;
+      break;
+    }
+  }
+  pj_sync<NW>();
+  return status;
+}
 
 }  // namespace
 
@@ -594,89 +705,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   __shared__ PState P;
   __shared__ double mom1[PJ_MAXB][3];
   const int t = blockIdx.x, l = threadIdx.x;
-  const MechDev& M = a.mech;
-  const int nb = M.nb, nd = M.nd, n6 = 6 * nb, n = n6 + nd, ldf = n + 1;
-  const double dt = a.dt;
-  double* A = PJ_F;                         // the Newton matrix, rebuilt and factored each iteration
-  double* G = PJ_F + (size_t)n * ldf;       // Gpos (nd x n6), fixed
-  set_states(P, a.cs + (size_t)t * 13 * nb, nb, dt, l);
-  if (l < nb) {  // (sq1 I - [w1 x]) J w1; setsolution!: (v2, w2) start at the current velocities
-    const double* w1 = P.wc[l];
-    double Jw[3];
-    for (int i = 0; i < 3; ++i) Jw[i] = M.J[l][i][0] * w1[0] + M.J[l][i][1] * w1[1] + M.J[l][i][2] * w1[2];
-    const double sq1 = sqrt(4.0 / (dt * dt) - (w1[0] * w1[0] + w1[1] * w1[1] + w1[2] * w1[2]));
-    const double cr[3] = {w1[1] * Jw[2] - w1[2] * Jw[1], w1[2] * Jw[0] - w1[0] * Jw[2], w1[0] * Jw[1] - w1[1] * Jw[0]};
-    for (int i = 0; i < 3; ++i) {
-      mom1[l][i] = sq1 * Jw[i] - cr[i];
-      P.s[6 * l + i] = P.vc[l][i];
-      P.s[6 * l + 3 + i] = w1[i];
-    }
-  }
-  if (l >= n6 && l < n) P.s[l] = 0.0;
-  for (int i = l; i < nd * n6; i += 64) G[i] = 0.0;
-  __builtin_amdgcn_wave_barrier();
-  if (l < M.nsub) subjoint_pose_jac(P, M.sub[l], n6, G);
-  __builtin_amdgcn_wave_barrier();
-  int status = 1, it = 0;
-  for (int k = 1; k <= a.iters; ++k) {
-    // ---- the Newton matrix and the residual at the current solution
-    for (int i = l; i < n * ldf; i += 64) A[i] = 0.0;
-    __builtin_amdgcn_wave_barrier();
-    if (l < M.nsub) {
-      subjoint(P, M.sub[l], n6, ldf, dt, true, true, false);  // g(x3, q3) and dg/d(v2, w2)
-    } else if (l < M.nsub + 9 * nb) {  // d/dw2 [(sq2 I + [w2 x]) J w2] (gprx/vi.py)
-      const int e = l - M.nsub, b = e / 9, i = (e - 9 * b) / 3, kk = e - 9 * b - 3 * i;
-      const double* w2 = P.s + 6 * b + 3;
-      double Jw[3];
-      for (int q = 0; q < 3; ++q) Jw[q] = M.J[b][q][0] * w2[0] + M.J[b][q][1] * w2[1] + M.J[b][q][2] * w2[2];
-      const double sq2 = sqrt(4.0 / (dt * dt) - (w2[0] * w2[0] + w2[1] * w2[1] + w2[2] * w2[2]));
-      const double sw[3][3] = {{0.0, -w2[2], w2[1]}, {w2[2], 0.0, -w2[0]}, {-w2[1], w2[0], 0.0}};
-      const double sj[3][3] = {{0.0, -Jw[2], Jw[1]}, {Jw[2], 0.0, -Jw[0]}, {-Jw[1], Jw[0], 0.0}};
-      const double swJ = sw[i][0] * M.J[b][0][kk] + sw[i][1] * M.J[b][1][kk] + sw[i][2] * M.J[b][2][kk];
-      A[(6 * b + 3 + i) * ldf + 6 * b + 3 + kk] = ((sq2 * M.J[b][i][kk] + swJ) - sj[i][kk]) - Jw[i] * w2[kk] / sq2;
-    } else if (l < M.nsub + 12 * nb) {
-      const int e = l - M.nsub - 9 * nb, b = e / 3, c = e - 3 * b;
-      A[(6 * b + c) * ldf + 6 * b + c] = M.m[b] / dt;
-    }
-    for (int e = l; e < n6 * nd; e += 64) {  // -Gpos^T (upper right), -reg I (lower right)
-      const int j = e / nd, r = e - j * nd;
-      A[j * ldf + n6 + r] = -G[(size_t)r * n6 + j];
-    }
-    if (l < nd && a.reg != 0.0) A[(n6 + l) * ldf + n6 + l] = -a.reg;
-    __builtin_amdgcn_wave_barrier();
-    if (l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, a.grav, l);
-    __builtin_amdgcn_wave_barrier();
-    // a system that is not finite (|w| beyond 2/dt: the reference's sqrt throws a DomainError) or is
-    // singular (SingularException) fails the state: its row is NaN
-    bool fin = l < n ? isfinite(P.f[l]) : true;
-    for (int i = l; i < n * ldf; i += 64) fin = fin && isfinite(A[i]);
-    if (__any(!fin)) {
-      status = 2;
-      break;
-    }
-    double bvec = l < n ? P.f[l] : 0.0;
-    if (lu_solve<1>(A, n, ldf, bvec) || __any(l < n && !isfinite(bvec))) {
-      status = 2;
-      break;
-    }
-    if (l < n) {
-      P.ds[l] = bvec;
-      P.s[l] = P.s[l] - bvec;
-    }
-    it = k;
-    __builtin_amdgcn_wave_barrier();
-    // ---- convergence: |f(s_new)| and |ds|
-    if (l < M.nsub) subjoint(P, M.sub[l], n6, ldf, dt, true, false, false);
-    __builtin_amdgcn_wave_barrier();
-    if (l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, a.grav, l);
-    __builtin_amdgcn_wave_barrier();
-    const double fv = l < n ? P.f[l] : 0.0, dv = l < n ? P.ds[l] : 0.0;
-    const double nf = sqrt(wsum(fv * fv)), nds = sqrt(wsum(dv * dv));
-    if (nf < a.eps && nds < a.eps) {
-      status = 0;
-      break;
-    }
-  }
+  const int nb = a.mech.nb;
+  set_states(P, a.cs + (size_t)t * 13 * nb, nb, a.dt, l);
+  int it;
+  const int status = vi_newton<1>(P, mom1, a.mech, a.dt, a.reg, a.eps, a.grav, a.iters, it);
   double* o = a.out + (size_t)t * 13 * nb;
   for (int i = l; i < 13 * nb; i += 64) {
     const int b = i / 13, k = i - 13 * b;
@@ -693,8 +725,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 }
 
 // ---- predictdynamics: one workgroup per trajectory, every step on the device --------------------
-template <int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_rollout_max(RolloutMaxArgs a) {
+// The MeanDynamics form (MD; predict_y = mu(obs) + k*^T alpha, src/mDynamics.jl:41-55) adds the physics
+// mean per step: a second LDS PState set from obs (what the stepwise path hands gprx_vi_step), the
+// variational-integrator solve on the whole workgroup (vi_newton), and v2 / w2 of its solution at
+// CState position vw[g] added to GP g's mean (getmu(vwindices)).  The solve's matrix shares the
+// dynamic LDS with the projection's F / A (they run one after the other); the second PState and
+// mom1 follow it there.  A failed physics step (status 2: the reference throws) stops the
+// trajectory with status 2; one that only runs out of iterations (status 1) is used as it is, as
+// the stepwise path uses it.
+// One template over the argument type: with RolloutMaxArgs (MeanZero) the instructions are those
+// of the kernel before the MeanDynamics form existed (compared in the disassembly; a shared
+// __device__ body called by two kernels changed its register allocation).  The MeanDynamics form
+// drops the four-waves-per-SIMD hint: in the 128 registers that leaves, the solve spills to scratch.
+__host__ __device__ inline size_t md_mat_doubles(int nb, int nd) {
+  const size_t n = 6 * (size_t)nb + nd, pj = 2 * n * (n + 1), vi = n * (n + 1) + (size_t)nd * 6 * nb;
+  return pj > vi ? pj : vi;
+}
+template <class Args>
+constexpr bool is_md = std::is_same_v<Args, RolloutMaxMdArgs>;
+template <int MODE, class Args>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(is_md<Args> ? 1 : 4, is_md<Args> ? 2 : 4)))
+void k_rollout_max(Args a) {
+  constexpr bool MD = is_md<Args>;
   constexpr int NT = 256, NW = NT / 64;
   __shared__ PState P;
   __shared__ double obs[13 * PJ_MAXB];
@@ -704,8 +756,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int nb = a.mech.nb, n6 = 6 * nb, d = a.d, G = a.G;
   const RolloutGP* gp = a.gps + (size_t)a.group[t] * G;
   const double* st0 = a.start + (size_t)t * d;
+  [[maybe_unused]] PState* Q = nullptr;            // the physics mean's state and (sq1 I - [w1 x]) J w1
+  [[maybe_unused]] double (*mom1)[3] = nullptr;
+  [[maybe_unused]] int vis = 0;
+  if constexpr (MD) {
+    Q = reinterpret_cast<PState*>(pj_lds() + md_mat_doubles(nb, a.mech.nd));
+    mom1 = reinterpret_cast<double (*)[3]>(Q + 1);
+  }
   if (w == 0) set_states(P, st0, nb, a.dt, l);
   for (int i = tid; i < d; i += NT) obs[i] = st0[i];
+  if constexpr (MD) {
+    // setstates! leaves the start's own velocities as the solution, which the closing updatestate!
+    // uses when steps = 0 (the MeanZero form, kept as it was, leaves P.s unset in that case)
+    if (tid < n6) P.s[tid] = st0[13 * (tid / 6) + 7 + tid % 6];
+  }
   if (tid == 0) {
     perr_s = 0.0;
     P.status = 0;
@@ -736,6 +800,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       if (l == 0) red[w][g] = sacc;
     }
     __syncthreads();
+    if constexpr (MD) {  // the physics mean at obs
+      if (w == 0) set_states(*Q, obs, nb, a.dt, l);
+      __syncthreads();
+      int vit;
+      const int vs = vi_newton<NW>(*Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
+      vis |= vs;
+      if (vs == 2) {  // the same on every wave
+        if (tid == 0) P.status = 2;
+        __syncthreads();
+        break;
+      }
+    }
     if (w == 0) {
       // getvw: mu_g at CState position vw[g], zero elsewhere; (v, w) per body into P.s
       if (l < n6) P.s[l] = 0.0;
@@ -744,6 +820,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         double mu = red[0][l];
         for (int q = 1; q < NW; ++q) mu += red[q][l];
         const int pos = a.vw[l], b = pos / 13, k = pos - 13 * b;  // k in 7..12
+        if constexpr (MD) mu += Q->s[6 * b + (k - 7)];
         P.s[6 * b + (k - 7)] = mu;
       }
     }
@@ -767,7 +844,201 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (l == 0) {
       a.perr[t] = P.status ? NAN : perr_s / (a.steps > 0 ? a.steps : 1);
       a.status[t] = P.status;
+      if constexpr (MD)
+        if (a.vi.status) a.vi.status[t] = vis;
     }
+  }
+}
+// ---- predictdynamicsmin with MeanDynamics GPs: one workgroup per trajectory ----------------------
+// The experiments' xtransform (examples/minimal_coordinates/*noise.jl, restated in
+// gprx/mdynamics.py xtransform, whose operation order this keeps) for body b: the CState of the
+// mechanism at the minimal coordinates (a0, a1) with rates (r0, r1), the linear velocities by the
+// reference's literal 0.01 finite difference of the positions (not dt).
+static __device__ __forceinline__ void min_cstate_body(int mech, int b, double a0, double r0, double a1, double r1, double l1, double l2, double* c) {
+  const double h = 0.01;
+  double x = 0.0, y, z, yn, zn, th, w;  // position (x, y, z), the advanced (yn, zn), angle about x and its rate
+  if (mech == 1) {  // P1
+    th = a0;
+    w = r0;
+    const double tn = th + w * h;
+    y = 0.5 * sin(th) * l1;
+    z = -0.5 * cos(th) * l1;
+    yn = 0.5 * sin(tn) * l1;
+    zn = -0.5 * cos(tn) * l1;
+  } else if (mech == 2) {  // P2: a1 relative to link 1
+    const double n1 = a0 + r0 * h, n2 = a1 + r1 * h;
+    if (b == 0) {
+      th = a0;
+      w = r0;
+      y = 0.5 * sin(a0) * l1;
+      z = -0.5 * cos(a0) * l1;
+      yn = 0.5 * sin(n1) * l1;
+      zn = -0.5 * cos(n1) * l1;
+    } else {
+      th = a0 + a1;
+      w = r0 + r1;
+      y = sin(a0) * l1 + 0.5 * sin(a0 + a1) * l2;
+      z = -cos(a0) * l1 - 0.5 * cos(a0 + a1) * l2;
+      yn = sin(n1) * l1 + 0.5 * sin(n1 + n2) * l2;
+      zn = -cos(n1) * l1 - 0.5 * cos(n1 + n2) * l2;
+    }
+  } else if (mech == 3) {  // CP: the cart at (0, a0, 0) moving with r0, the pole at angle a1
+    if (b == 0) {
+      for (int k = 0; k < 13; ++k) c[k] = 0.0;
+      c[1] = a0;
+      c[3] = 1.0;
+      c[8] = r0;
+      return;
+    }
+    th = a1;
+    w = r1;
+    const double tn = w * h + th;
+    y = a0 + 0.5 * sin(th) * l1;
+    z = -0.5 * cos(th) * l1;
+    yn = a0 + r0 * h + 0.5 * sin(tn) * l1;
+    zn = -0.5 * cos(tn) * l1;
+  } else {  // FB: links 1 and 4 turn with a0, links 2 and 3 with a1
+    const double na = 0.01 * r0 + a0, nb = 0.01 * r1 + a1;
+    const bool first = b == 0 || b == 3;
+    th = first ? a0 : a1;
+    w = first ? r0 : r1;
+    if (b == 0 || b == 2) {
+      const double t = b == 0 ? a0 : a1, tn = b == 0 ? na : nb;
+      y = 0.5 * sin(t) * l1;
+      z = -0.5 * cos(t) * l1;
+      yn = 0.5 * sin(tn) * l1;
+      zn = -0.5 * cos(tn) * l1;
+    } else {
+      const double p = b == 1 ? a0 : a1, q = b == 1 ? a1 : a0, pn = b == 1 ? na : nb, qn = b == 1 ? nb : na;
+      y = sin(p) * l1 + 0.5 * sin(q) * l1;
+      z = -cos(p) * l1 - 0.5 * cos(q) * l1;
+      yn = sin(pn) * l1 + 0.5 * sin(qn) * l1;
+      zn = -cos(pn) * l1 - 0.5 * cos(qn) * l1;
+    }
+  }
+  c[0] = x;
+  c[1] = y;
+  c[2] = z;
+  c[3] = cos(th / 2.0);
+  c[4] = sin(th / 2.0);
+  c[5] = 0.0;
+  c[6] = 0.0;
+  c[7] = (x - x) / h;
+  c[8] = (yn - y) / h;
+  c[9] = (zn - z) / h;
+  c[10] = w;
+  c[11] = 0.0;
+  c[12] = 0.0;
+}
+
+// Per step (examples/utils/predictdynamics.jl:30-102 with src/mDynamics.jl:41-55): the features of
+// (q_old, qdot_old) as k_rollout builds them, the nc GP means there (k_rollout_max's loop, both
+// distance modes), the CState of the features (min_cstate_body; the angle is atan2(sin, cos) when
+// usesin), set_states and vi_newton on the whole workgroup, the rates read from the solution
+// (gprx/mdynamics.py MIN_IDX / mean_min), rate = GP mean + physics rate, and k_rollout's explicit
+// round-to-nearest update.  Every thread keeps the coordinates (the same values).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_rollout_min_md(RolloutMinMdArgs a) {
+  constexpr int NT = 256, NW = NT / 64;
+  __shared__ PState Q;
+  __shared__ double mom1[PJ_MAXB][3];
+  __shared__ double cs[13 * PJ_MAXB];
+  __shared__ double red[NW][2];
+  const int t = blockIdx.x, tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  const int nc = a.nc, d = a.d, nb = a.mech.nb;
+  const RolloutGP* gp = a.gps + (size_t)a.group[t] * nc;
+  double qo[2], vo[2], qc[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    qo[c] = c < nc ? a.start[(size_t)t * 2 * nc + 2 * c] : 0.0;
+    vo[c] = c < nc ? a.start[(size_t)t * 2 * nc + 2 * c + 1] : 0.0;
+    qc[c] = __dadd_rn(qo[c], __dmul_rn(a.dt, vo[c]));
+  }
+  const bool s0 = a.usesin && a.ang0, s1 = a.usesin && a.ang1;
+  const int w0 = s0 ? 3 : 2;
+  int vis = 0;
+  bool failed = false;
+  for (int step = 0; step < a.steps; ++step) {
+    const double e0[3] = {s0 ? sin(qo[0]) : qo[0], s0 ? cos(qo[0]) : vo[0], s0 ? vo[0] : 0.0};
+    const double e1[3] = {s1 ? sin(qo[1]) : qo[1], s1 ? cos(qo[1]) : vo[1], s1 ? vo[1] : 0.0};
+    double ov[ROLLOUT_DMAX];
+#pragma unroll
+    for (int p = 0; p < ROLLOUT_DMAX; ++p) {
+      const int q = p - w0;
+      ov[p] = p < w0 ? (p == 0 ? e0[0] : (p == 1 ? e0[1] : e0[2])) : (q == 0 ? e1[0] : (q == 1 ? e1[1] : (q == 2 ? e1[2] : 0.0)));
+    }
+    // ---- mu_g = sum_j sf2 exp(-r_j / 2) alpha_j at the features
+    for (int g = 0; g < nc; ++g) {
+      const RolloutGP Gp = gp[g];
+      const double sf2 = Gp.params[d];
+      double sacc = 0.0;
+      for (int j = tid; j < Gp.N; j += NT) {
+        const double* x = Gp.X + (size_t)j * d;
+        double r = 0.0;
+#pragma unroll
+        for (int p = 0; p < ROLLOUT_DMAX; ++p) {
+          if (p < d) {
+            const double o = ov[p];
+            if (MODE == 0) {
+              const double v = fma(-2.0, x[p] * o, x[p] * x[p] + o * o);
+              r = r + (v > 0.0 ? v : 0.0) * Gp.params[p];
+            } else {
+              const double df = x[p] - o;
+              r = __builtin_fma(df * df, Gp.params[p], r);
+            }
+          }
+        }
+        sacc = fma(sf2 * exp(-r * 0.5), Gp.alpha[j], sacc);
+      }
+      sacc = wsum(sacc);
+      if (l == 0) red[w][g] = sacc;
+    }
+    // ---- the physics mean: CState of the features, one variational-integrator step
+    const double a0 = s0 ? atan2(e0[0], e0[1]) : e0[0], r0 = s0 ? e0[2] : e0[1];
+    const double a1 = s1 ? atan2(e1[0], e1[1]) : e1[0], r1 = s1 ? e1[2] : e1[1];
+    if (w == 0 && l < nb) min_cstate_body(a.mech_id, l, a0, r0, a1, r1, a.len[0], a.len[1], cs + 13 * l);
+    __syncthreads();
+    if (w == 0) set_states(Q, cs, nb, a.dt, l);
+    __syncthreads();
+    int vit;
+    const int vs = vi_newton<NW>(Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
+    vis |= vs;
+    if (vs == 2) {  // the same on every wave: the reference throws, the trajectory stops
+      failed = true;
+      break;
+    }
+    // the solution's rates (0-based CState positions 13 b + k, k >= 7, at Q.s[6 b + k - 7]):
+    // P1 [11]; P2 (w1, w2 - w1) of bodies 1 and 2; CP [9, 24]; FB [11, 37] (1-based)
+    double phys[2];
+    if (a.mech_id == 2) {
+      phys[0] = Q.s[3];
+      phys[1] = Q.s[9] - Q.s[3];
+    } else if (a.mech_id == 3) {
+      phys[0] = Q.s[1];
+      phys[1] = Q.s[9];
+    } else {
+      phys[0] = Q.s[3];
+      phys[1] = a.mech_id == 4 ? Q.s[15] : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      double v = red[0][c];
+#pragma unroll
+      for (int q = 1; q < NW; ++q) v += red[q][c];
+      const double rate = c < nc ? v + phys[c] : 0.0;
+      qo[c] = qc[c];
+      vo[c] = rate;
+      qc[c] = __dadd_rn(qc[c], __dmul_rn(rate, a.dt));
+    }
+    __syncthreads();  // red, cs and Q are rewritten by the next step
+  }
+  if (tid == 0) {
+    for (int c = 0; c < nc; ++c) {
+      a.out[(size_t)t * 2 * nc + 2 * c] = failed ? NAN : qc[c];
+      a.out[(size_t)t * 2 * nc + 2 * c + 1] = failed ? NAN : vo[c];
+    }
+    a.status[t] = failed ? 2 : 0;
+    if (a.vi.status) a.vi.status[t] = vis;
   }
 }
 
@@ -783,8 +1054,22 @@ void launch_vi_step(const ViArgs& a, hipStream_t s) {
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s) {
   if (a.T <= 0) return;
   const size_t lds = pj_lds_bytes(a.mech.nb, a.mech.nd);
-  if (dist_mode == 0) hipLaunchKernelGGL(k_rollout_max<0>, dim3(a.T), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(k_rollout_max<1>, dim3(a.T), dim3(256), lds, s, a);
+  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, RolloutMaxArgs>), dim3(a.T), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((k_rollout_max<1, RolloutMaxArgs>), dim3(a.T), dim3(256), lds, s, a);
+}
+void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s) {
+  if (a.T <= 0) return;
+  // [the larger of the projection's F / A and the solve's matrix + Gpos | the solve's PState | mom1]
+  const size_t lds = md_mat_doubles(a.mech.nb, a.mech.nd) * sizeof(double) + sizeof(PState) + sizeof(double) * 3 * PJ_MAXB;
+  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((k_rollout_max<1, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
+}
+void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s) {
+  if (a.T <= 0) return;
+  const size_t n = 6 * (size_t)a.mech.nb + a.mech.nd;
+  const size_t lds = (n * (n + 1) + (size_t)a.mech.nd * 6 * a.mech.nb) * sizeof(double);  // launch_vi_step's
+  if (dist_mode == 0) hipLaunchKernelGGL(k_rollout_min_md<0>, dim3(a.T), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(k_rollout_min_md<1>, dim3(a.T), dim3(256), lds, s, a);
 }
 
 }  // namespace gprx

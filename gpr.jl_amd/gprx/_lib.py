@@ -100,6 +100,10 @@ SIGNATURES = {
                                 _ip]),
     "gprx_rollout_max": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _ip, C.c_int,
                                    _ip, C.c_int, _ip, _dp, _dp, _dp, _ip]),
+    "gprx_rollout_max_md": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_vp), _ip,
+                                      C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip]),
+    "gprx_rollout_min_md": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _ip,
+                                      C.c_int, _ip, _dp, _dp, _ip, _ip]),
     "gprx_cstate_pack": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gprx_select_outputs": (C.c_int, [_dp, C.c_int, C.c_int, _ip, C.c_int, _dp]),
 }

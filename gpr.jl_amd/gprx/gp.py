@@ -57,6 +57,47 @@ class MeanFunction:
         return np.array([self._at(X[:, t]) for t in range(X.shape[1])])
 
 
+class MeanDynamics:
+    """GPR.MeanDynamics(mechanism, getμ, μID; xtransform) (src/mDynamics.jl:13-55) for the experiment
+    mechanisms: the prior mean is output mu_id (1-based, as μID) of one variational-integrator step
+    at the input, solved on the device (gprx.mdynamics -> gprx_vi_step).  variant names the
+    experiment's input and getμ: "max" (CState inputs, getμ(vωindices)), "min" or "min_sin"
+    (minimal coordinates through the experiments' xtransform, the solution's rates).  No
+    hyper-parameters (mDynamics.jl:29).  GPEs that carry it roll out in one launch through
+    gprx.projection.predictdynamics_md / gprx.rollout.rollout_min_md."""
+
+    VARIANTS = ("max", "min", "min_sin")
+
+    def __init__(self, mech: str, mu_id: int, variant: str = "max", ctx: Context | None = None):
+        from .rollout import MECH, NCOORD
+
+        if mech not in MECH:
+            raise ValueError(f"Experiment {mech} not supported!")
+        if variant not in self.VARIANTS:
+            raise ValueError(f"variant must be one of {self.VARIANTS}")
+        from .data import VW_INDICES
+
+        nout = len(VW_INDICES[mech]) if variant == "max" else NCOORD[mech]
+        if not 1 <= int(mu_id) <= nout:
+            raise ValueError(f"mu_id must be in 1..{nout} for {mech} {variant}")
+        self.mech, self.mu_id, self.variant, self.ctx = mech, int(mu_id), variant, ctx
+
+    def num_params(self) -> int:
+        return 0
+
+    def mean(self, X) -> np.ndarray:
+        from . import mdynamics
+
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        if self.variant == "max":
+            mu = mdynamics.mean_max(self.mech, X, ctx=self.ctx)
+        else:
+            mu = mdynamics.mean_min(self.mech, X, self.variant == "min_sin", ctx=self.ctx)
+        return mu[self.mu_id - 1].copy()
+
+
 class SEArd:
     """SEArd(ll, lσ): squared-exponential ARD kernel, ll = log length scales, lσ = log σ_f."""
 

@@ -14,6 +14,9 @@ The physics step runs on the device (k_vi_step through gprx.projection.vi_step, 
 state); gprx.vi holds the host restatement it is tested against (tests/test_vi.py,
 tests/test_vi_device.py).  Every function takes `physics` (a callable (mech, states) -> (solution,
 iterations, status)) to run the same logic on another implementation, e.g. physics=vi.vi_step.
+rollout_max / rollout_min are that stepwise path (three blocking device calls per step);
+rollout_max_device / rollout_min_device run every step of every trajectory in one launch
+(k_rollout_max's MeanDynamics form, k_rollout_min_md).
 
 Maximal coordinates (e.g. examples/maximal_coordinates/P2noise.jl:28-33): the CState input,
 getμ(vωindices) of the solution CState.  Minimal coordinates (e.g. minimal_coordinates/
@@ -224,3 +227,47 @@ def rollout_min(mech: str, rb, trials: list[int], starts, steps: int, usesin: bo
         q_cur = q_cur + rates * DT
     keep = np.asarray(trials, dtype=int)
     return np.stack([np.stack([final_cstate(mech, q_cur[i, j]) for j in range(M)]) for i in keep])
+
+
+def _device_groups(rb, trials, starts):
+    """The kept trials as rollout groups of rb's slots, their starts one after another and each
+    trajectory's group: no padding dummies, the trials left out are simply not launched."""
+    keep = [int(i) for i in trials]
+    S = np.asarray(starts, dtype=np.float64)
+    groups = [[(rb.batch, rb.slot(i, g)) for g in range(rb.G)] for i in keep]
+    M = S.shape[1]
+    start = S[keep].reshape(len(keep) * M, -1)
+    tg = np.repeat(np.arange(len(keep), dtype=np.int32), M)
+    return groups, start, tg, len(keep), M
+
+
+def rollout_max_device(mech: str, rb, trials: list[int], starts, steps: int, regularizer=None, ctx=None):
+    """rollout_max's arguments and return values, with every step of every trajectory in ONE device
+    launch (gprx.projection.predictdynamics_md -> gprx_rollout_max_md) instead of three blocking
+    calls per step.  status: 1 = singular projection, 2 = a failed physics step (the row is NaN, as
+    the stepwise path leaves it)."""
+    from .projection import predictdynamics_md
+
+    groups, start, tg, n, M = _device_groups(rb, trials, starts)
+    if n == 0:
+        d = np.asarray(starts).shape[-1]
+        return np.zeros((0, M, d)), np.zeros((0, M)), np.zeros((0, M), dtype=np.int32)
+    fin, pe, st, _ = predictdynamics_md(mech, groups, start, steps, data.VW_INDICES[mech], regularizer, traj_group=tg,
+                                        dt=DT, ctx=ctx)
+    return fin.reshape(n, M, -1), pe.reshape(n, M), st.reshape(n, M)
+
+
+def rollout_min_device(mech: str, rb, trials: list[int], starts, steps: int, usesin: bool, ctx=None):
+    """rollout_min's arguments and return value (the final CStates, NaN where a physics step failed),
+    with every step in ONE device launch (gprx.rollout.rollout_min_md -> gprx_rollout_min_md)."""
+    from .projection import NBODIES
+    from .rollout import rollout_min_md
+
+    groups, start, tg, n, M = _device_groups(rb, trials, starts)
+    nb13 = 13 * NBODIES[mech]
+    if n == 0:
+        return np.zeros((0, M, nb13))
+    fin, _, _ = rollout_min_md(mech, groups, start, steps, usesin, DT, traj_group=tg, ctx=ctx)
+    q = fin[:, 0::2].reshape(n, M, -1)
+    return np.stack([np.stack([final_cstate(mech, q[i, j]) if np.all(np.isfinite(q[i, j])) else np.full(nb13, np.nan)
+                               for j in range(M)]) for i in range(n)])

@@ -124,6 +124,50 @@ def predictdynamics(mech: str, groups, start, steps: int, vw_indices, regularize
     return out, pe, st
 
 
+def predictdynamics_md(mech: str, groups, start, steps: int, vw_indices, regularizer: float | None = None,
+                       vi_regularizer: float | None = None, traj_group=None, dt: float = DT, ctx: Context | None = None):
+    """predictdynamics with MeanDynamics GPs (predict_y = μ(obs) + k*ᵀα, src/mDynamics.jl:41-55) in one
+    device launch (gprx_rollout_max_md): per step the G GP means plus getμ(vωindices) of one
+    variational-integrator step at the current CState, then getvw, projectv! and updatestate!.
+    Arguments as predictdynamics; the GPs are (GPBatch, slot) pairs factorised on y - μ(X) or GPEs
+    that carry MeanDynamics(mech, g + 1, "max").  Returns (final CStates (T, 13 nb), mean projection
+    error per step (T,), status (T,): 1 = singular projection, 2 = a failed physics step, the row is
+    NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
+    from . import vi
+    from .rollout import _slot_ref_md
+
+    if mech not in MECH:
+        raise ValueError(f"Experiment {mech} not supported!")
+    nb = NBODIES[mech]
+    S = np.ascontiguousarray(np.atleast_2d(start), dtype=np.float64)
+    T = S.shape[0]
+    if S.shape != (T, 13 * nb):
+        raise ValueError(f"start must be (T, {13 * nb})")
+    G = len(vw_indices)
+    refs = []
+    for grp in groups:
+        if len(grp) != G:
+            raise ValueError(f"each group needs {G} GPs (one per vw index)")
+        refs += [_slot_ref_md(g, mech, "max", k) for k, g in enumerate(grp)]
+    tg = np.zeros(T, dtype=np.int32) if traj_group is None else np.ascontiguousarray(traj_group, dtype=np.int32)
+    if tg.shape != (T,):
+        raise ValueError("traj_group must have one entry per trajectory")
+    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
+    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
+    vwi = np.ascontiguousarray(vw_indices, dtype=np.int32)
+    reg = REGULARIZER[mech] if regularizer is None else float(regularizer)
+    vreg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
+    ctx = ctx or refs[0][0].ctx
+    out = np.empty((T, 13 * nb))
+    pe = np.empty(T)
+    st = np.empty(T, dtype=np.int32)
+    vst = np.empty(T, dtype=np.int32)
+    L.check(L.lib.gprx_rollout_max_md(ctx.h, MECH[mech], float(dt), int(steps), reg, vreg, len(groups), batches, L.iptr(slots),
+                                      G, L.iptr(vwi), T, L.iptr(tg), L.dptr(S), L.dptr(out), L.dptr(pe), L.iptr(st),
+                                      L.iptr(vst)), ctx.h)
+    return out, pe, st, vst
+
+
 def _default_ctx():
     """The context of this process's device, in this order:
       * GPRX_DEVICE (an explicit device index);

@@ -14,7 +14,8 @@ Coordinates (startobservation layout, predictdynamics.jl:40,54,71,86):
     CP  (x, v, theta, omega)                 -> 2 GPs (v, omega)
     FB  (theta1, omega1, theta3, omega3)     -> 2 GPs (omega1, omega3)
 GP inputs per step: that vector, or with usesin (sin q, cos q, qdot) for the angle coordinates.
-Only MeanZero GPs roll out on the device (MeanDynamics needs a physics solve per step).
+rollout_min / predictdynamicsmin take MeanZero GPs; MeanDynamics GPs, whose mean is a physics solve per
+step, roll out through rollout_min_md (gprx_rollout_min_md: the solve runs in the same launch).
 """
 from __future__ import annotations
 
@@ -84,8 +85,69 @@ def _slot_ref(g):
         return b, int(s)
     from .gp import MeanZero  # GPE
     if not isinstance(g.mean, MeanZero):
-        raise NotImplementedError("device rollouts need MeanZero GPs (MeanDynamics solves physics per step)")
+        raise NotImplementedError("device rollouts need MeanZero GPs (MeanDynamics solves physics per step: "
+                                  "predictdynamics_md / rollout_min_md)")
     return g._batch, 0
+
+
+def _slot_ref_md(g, mech: str, variant: str, k: int):
+    """GP k (0-based) of a MeanDynamics rollout group: a (GPBatch, slot) pair factorised on
+    y - μ(X), or a GPE whose mean is MeanDynamics(mech, k + 1, variant)."""
+    if isinstance(g, tuple):
+        return _slot_ref(g)
+    from .gp import MeanDynamics
+    if not isinstance(g.mean, MeanDynamics):
+        raise NotImplementedError("MeanDynamics rollouts need MeanDynamics GPs (MeanZero GPs roll out through "
+                                  "predictdynamics / rollout_min)")
+    m = g.mean
+    if (m.mech, m.variant, m.mu_id) != (mech, variant, k + 1):
+        raise ValueError(f"GP {k} of a {mech} {variant} group needs MeanDynamics({mech!r}, {k + 1}, {variant!r}), "
+                         f"not ({m.mech!r}, {m.mu_id}, {m.variant!r})")
+    return g._batch, 0
+
+
+def rollout_min_md(mech: str, groups, start, steps: int, usesin: bool = False, dt: float = DT,
+                   vi_regularizer: float | None = None, traj_group=None, ctx: Context | None = None):
+    """rollout_min with MeanDynamics GPs (predict_y = μ(obs) + k*ᵀα, src/mDynamics.jl:41-55) in one
+    device launch (gprx_rollout_min_md): per step the GP means at the features plus the rates of one
+    variational-integrator step at the experiments' xtransform of the features.  groups as
+    rollout_min's, of (GPBatch, slot) pairs factorised on y - μ(X) or GPEs that carry
+    MeanDynamics(mech, g + 1, "min" / "min_sin").  Returns (final (T, 2nc), status (T,): 2 = a failed
+    physics step, the row is NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
+    from . import vi
+
+    if mech not in MECH:
+        raise ValueError(f"Experiment {mech} not supported!")
+    nc = NCOORD[mech]
+    start = np.ascontiguousarray(start, dtype=np.float64)
+    if start.ndim == 1:
+        start = start[None, :]
+    T = start.shape[0]
+    if start.shape != (T, 2 * nc):
+        raise ValueError(f"start must be (T, {2 * nc})")
+    if traj_group is None:
+        traj_group = np.zeros(T, dtype=np.int32)
+    traj_group = np.ascontiguousarray(traj_group, dtype=np.int32)
+    if traj_group.shape != (T,):
+        raise ValueError("traj_group must have one entry per trajectory")
+    refs = []
+    for grp in groups:
+        if len(grp) != nc:
+            raise ValueError(f"{mech} rollouts use {nc} GP(s) per group")
+        refs += [_slot_ref_md(g, mech, "min_sin" if usesin else "min", k) for k, g in enumerate(grp)]
+    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
+    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
+    reg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
+    ctx = ctx or refs[0][0].ctx
+    out = np.empty((T, 2 * nc), dtype=np.float64)
+    st = np.empty(T, dtype=np.int32)
+    vst = np.empty(T, dtype=np.int32)
+    L.check(
+        L.lib.gprx_rollout_min_md(ctx.h, MECH[mech], 1 if usesin else 0, float(dt), int(steps), reg, len(groups), batches,
+                                  L.iptr(slots), T, L.iptr(traj_group), L.dptr(start), L.dptr(out), L.iptr(st), L.iptr(vst)),
+        ctx.h,
+    )
+    return out, st, vst
 
 
 def _rotx_q(th):

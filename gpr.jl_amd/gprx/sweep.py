@@ -59,6 +59,7 @@ ETYPE = {"max": "noisy", "min": "noisy", "min_sin": "noisysin", "md_max": "noisy
 # host restatement of ConstrainedDynamics 0.7.4's variational-integrator step (gprx.vi), which is not
 # in the reference tree: its only cross-check is the repo's own action-based oracle/vi_oracle.py
 # (same modelling assumptions), so those entries are not reference-equivalent numbers.
+MD_ROLLOUTS = ("stepwise", "device")  # run_group's md_rollout
 PARITY = {"max": "gp: oracle-pinned; physics: projectv! restated (unpinned vs ConstrainedDynamics)",
           "min": "gp: oracle-pinned", "min_sin": "gp: oracle-pinned",
           "vi": "unpinned: gprx.vi restates ConstrainedDynamics 0.7.4 newton! (absent from the reference tree)",
@@ -109,13 +110,18 @@ def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, c
 
 def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
               max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
-              trials: list | None = None, budget: int | None = None) -> dict:
+              trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise") -> dict:
     """One (mechanism, N, variant) group for this rank's trials: device optimise of every GP,
     then the variant's evaluation.  Returns per-trial arrays (n_local, ...) and timings.
     trials: prebuilt local_trials-shaped inputs (the hyper-parameter search's), else noise.jl's.
     The trials run as one device batch when they fit `budget` bytes (None: the free HBM,
     shard.default_budget), else as several batches one after another (shard.group_plan), with
-    bit-identical results; keep=True (the batch returned for inspection) needs one batch."""
+    bit-identical results; keep=True (the batch returned for inspection) needs one batch.
+    md_rollout: how the md_* variants roll out -- "stepwise" (a host loop of three device calls per
+    step, gprx.mdynamics.rollout_max / rollout_min) or "device" (every step in one launch,
+    gprx.mdynamics.rollout_max_device / rollout_min_device)."""
+    if md_rollout not in MD_ROLLOUTS:
+        raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")
     if trials is None:
         trials = local_trials(mech, N, variant, trial_ids, testsamples, ctx)
     n = len(trials)
@@ -127,7 +133,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     parts = []
     for lo, hi, nd in plan:
         rb = shard.RankBatch(trials[lo:hi], ctx=ctx, dev_trials=nd)
-        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit)
+        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout)
         if keep:
             part.update(rb=rb, trials=trials)
         else:
@@ -142,7 +148,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     return out
 
 
-def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit) -> dict:
+def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise") -> dict:
     """run_group's work for the trials of one device batch rb."""
     from .optim import LBFGS, Options
 
@@ -184,7 +190,8 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
         good = [i for i in range(n) if np.all(ok_gp[i])]
         if good:
             starts = np.stack([trials[i]["Xs"].T for i in range(n)])  # (n, M, d)
-            fin, pe, st = mdynamics.rollout_max(mech, rb, good, starts, simsteps, ctx=ctx)
+            roll = mdynamics.rollout_max_device if md_rollout == "device" else mdynamics.rollout_max
+            fin, pe, st = roll(mech, rb, good, starts, simsteps, ctx=ctx)
             for k, i in enumerate(good):
                 if np.any(st[k] != 0) or np.isnan(fin[k]).any():  # singular projection / failed physics mean
                     continue
@@ -196,7 +203,8 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
         good = [i for i in range(n) if np.all(ok_gp[i])]
         if good:
             starts = np.stack([trials[i]["start"] for i in range(n)])  # (n, M, 2 nc)
-            fin = mdynamics.rollout_min(mech, rb, good, starts, simsteps, usesin=variant == "md_min_sin", ctx=ctx)
+            roll = mdynamics.rollout_min_device if md_rollout == "device" else mdynamics.rollout_min
+            fin = roll(mech, rb, good, starts, simsteps, usesin=variant == "md_min_sin", ctx=ctx)
             for k, i in enumerate(good):
                 if np.isnan(fin[k]).any():  # a failed physics mean (vi_step status 2) throws in the reference
                     continue
@@ -252,7 +260,8 @@ def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int 
 
 
 def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
-        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None) -> dict:
+        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None,
+        md_rollout: str = "stepwise") -> dict:
     """The sweep.  Every rank runs its trials of every group; rank 0 returns the gathered
     checkpoint dict (other ranks None).  Without an initialised process group: one rank."""
     from .batch import Context
@@ -288,7 +297,7 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
             for var in variants:
                 if var == "vi":
                     continue
-                r = run_group(mech, N, var, mine, ctx, testsamples, simsteps, max_evals, time_limit)
+                r = run_group(mech, N, var, mine, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout=md_rollout)
                 local = {"kstep_mse": r.get("kstep_mse", np.zeros(0)), "perr": r.get("projectionerror", np.zeros(0)),
                          "failed": r.get("failed", np.zeros(0, dtype=bool)).astype(np.float64),
                          "ok": np.all(r["status"] == 0, axis=1).astype(np.float64) if r else np.zeros(0),
@@ -333,6 +342,8 @@ def main(argv=None):
     ap.add_argument("--simsteps", type=int, default=20)
     ap.add_argument("--max-evals", type=int, default=30, help="evaluation budget per GP (<= 0: none, as Optim's f_calls_limit)")
     ap.add_argument("--time-limit", type=float, default=float("nan"), help="seconds per group call (NaN: none)")
+    ap.add_argument("--md-rollout", choices=MD_ROLLOUTS, default="stepwise",
+                    help="the md_* variants' rollout: a host loop of device calls per step, or one device launch")
     ap.add_argument("--out", default="gpurun_out/sweep_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -350,7 +361,7 @@ def main(argv=None):
     res = run([m for m in a.mechs.split(",") if m], [int(s) for s in a.sizes.split(",") if s],
               [v for v in a.variants.split(",") if v], a.trials, a.testsamples, a.simsteps,
               a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True))
+              log=lambda s: print(s, flush=True), md_rollout=a.md_rollout)
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

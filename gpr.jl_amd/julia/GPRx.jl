@@ -193,6 +193,55 @@ function rollout_min(etype::String, gps::Vector{<:GPE}, startobservations::Vecto
     return [fin[:, t] for t in 1:T]
 end
 
+# The same two rollouts with MeanDynamics GPs (predict_y = μ(obs) + k*ᵀα, src/mDynamics.jl:41-55) in
+# one device launch each: the handles hold y - μ(X) (handle()), the device solves the physics mean
+# at every step.  vi_regularizer: the impulses' regularisation of the physics step (1e-10 for the
+# four-bar).  status 2 / a NaN column: a physics step failed (the reference throws); vi_status: OR
+# of the per-step physics statuses.  Argument types follow include/gprx.h; like the rest of this
+# file they have not been run (no Julia runtime in the build container).
+vi_regularizer(etype::String) = etype == "FB" ? 1e-10 : 0.0
+
+# predictdynamicsmin (examples/utils/predictdynamics.jl:30-102) with MeanDynamics GPs
+function rollout_min_md(etype::String, gps::Vector{<:GPE}, startobservations::Vector{Vector{Float64}},
+                        steps::Integer; usesin::Bool=false, Δt::Real=0.01)
+    haskey(MECH, etype) || throw(ArgumentError("Experiment $etype not supported!"))
+    any(gp -> gp.mean isa MeanZero, gps) && error("gprx: MeanZero GPs roll out through rollout_min")
+    T = length(startobservations)
+    nc = etype == "P1" ? 1 : 2
+    fin = zeros(2nc, T)
+    status, vi_status = zeros(Cint, T), zeros(Cint, T)
+    bs = [ccall((:gprx_gp_batch, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), handle(gp).ptr) for gp in gps]
+    rc = ccall((:gprx_rollout_min_md, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cdouble, Cint, Cdouble, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}),
+               context(), MECH[etype], Cint(usesin), Float64(Δt), Cint(steps), vi_regularizer(etype), Cint(1), bs,
+               zeros(Cint, nc), Cint(T), zeros(Cint, T), reduce(hcat, startobservations), fin, status, vi_status)
+    check(rc, gps)
+    return [fin[:, t] for t in 1:T], status, vi_status
+end
+
+# predictdynamics (examples/utils/predictdynamics.jl:7-22) with MeanDynamics GPs for all test CStates
+# of one trial: gps[g] predicts CState position vωindices[g] (1-based, as the experiments' getvω)
+function rollout_max_md(etype::String, gps::Vector{<:GPE}, startobservations::Vector{Vector{Float64}},
+                        steps::Integer, vωindices::Vector{<:Integer}; regularizer::Real=0.0, Δt::Real=0.01)
+    haskey(MECH, etype) || throw(ArgumentError("Experiment $etype not supported!"))
+    any(gp -> gp.mean isa MeanZero, gps) && error("gprx: MeanZero GPs roll out through gprx_rollout_max")
+    length(gps) == length(vωindices) || throw(ArgumentError("one GP per vω index"))
+    T, G = length(startobservations), length(gps)
+    d = length(startobservations[1])
+    fin, perr = zeros(d, T), zeros(T)
+    status, vi_status = zeros(Cint, T), zeros(Cint, T)
+    bs = [ccall((:gprx_gp_batch, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), handle(gp).ptr) for gp in gps]
+    rc = ccall((:gprx_rollout_max_md, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cdouble, Cint, Cdouble, Cdouble, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}),
+               context(), MECH[etype], Float64(Δt), Cint(steps), Float64(regularizer), vi_regularizer(etype), Cint(1), bs,
+               zeros(Cint, G), Cint(G), Vector{Cint}(vωindices), Cint(T), zeros(Cint, T),
+               reduce(hcat, startobservations), fin, perr, status, vi_status)
+    check(rc, gps)
+    return [fin[:, t] for t in 1:T], perr, status, vi_status
+end
+
 # gprx_opt_options (include/gprx.h): same field order and C layout
 struct OptOptions
     m::Cint

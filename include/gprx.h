@@ -325,6 +325,34 @@ int gprx_rollout_max(gprx_ctx* ctx, int mech, double dt, int steps, double regul
                      const int* traj_group, const double* start, double* final_state, double* proj_err,
                      int* status);
 
+/* ---- rollouts with MeanDynamics GPs: predict_y(gp, obs) = mu(obs) + k*^T alpha ------------------
+ * The GPs are (batch, slot) pairs factorised on y - mu(X); mu is one variational-integrator step
+ * of the mechanism (src/mDynamics.jl:41-55; gprx_vi_step), solved on the device at every step's
+ * state with newton_iter = 100, eps = 1e-10 and gravity 9.81 (gprx_vi_step's callers' values) and
+ * the impulses' regularisation vi_regularizer (1e-10 for the four-bar, 0 otherwise).  One launch
+ * runs every step of every trajectory.  A physics step that fails (gprx_vi_step status 2: the
+ * reference throws) stops its trajectory: status[t] = 2 and a NaN output row; one that does not
+ * converge within newton_iter (status 1) is used as it is.  vi_status (may be NULL): the OR of the
+ * trajectory's per-step physics statuses.                                                        */
+/* predictdynamics (examples/utils/predictdynamics.jl:7-22) with the mean of src/mDynamics.jl:41-55:
+ * gprx_rollout_max's arguments and outputs; per step mu_g = GP mean + v2 / w2 of the physics
+ * solution at CState position vw_idx1[g] (getmu(vwindices)), then getvw, projectv! and
+ * updatestate!.  status[t]: 0 ok, 1 singular projection, 2 failed physics mean.                   */
+int gprx_rollout_max_md(gprx_ctx* ctx, int mech, double dt, int steps, double regularizer, double vi_regularizer,
+                        int ngroups, gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1,
+                        int T, const int* traj_group, const double* start,
+                        double* final_state, double* proj_err, int* status, int* vi_status);
+/* predictdynamicsmin (examples/utils/predictdynamics.jl:30-102) with the mean of
+ * src/mDynamics.jl:41-55: gprx_rollout_min's arguments and outputs; per step the experiments'
+ * xtransform builds the CState from the GP input (the angle by atan2(sin, cos) when usesin, the
+ * linear velocities by the literal 0.01 finite difference), and the rate of coordinate g is the GP
+ * mean plus the physics solution's rate (P1 w1; P2 w1, w2 - w1; CP v1_y, w2; FB w1, w3).
+ * status[t]: 0 ok, 2 failed physics mean.                                                        */
+int gprx_rollout_min_md(gprx_ctx* ctx, int mech, int usesin, double dt, int steps, double vi_regularizer,
+                        int ngroups, gprx_batch* const* batches, const int* slots,
+                        int T, const int* traj_group, const double* start,
+                        double* final_state, int* status, int* vi_status);
+
 /* ---- host-side CState helpers (bit-exact copies) ------------------------------------------ */
 /* out[13*b + 0..12] = [xc(3), qc.w, qc.x, qc.y, qc.z, vc(3), wc(3)] for body b (CState.jl:20,26) */
 int gprx_cstate_pack(int nbodies, const double* xc, const double* qc_wxyz, const double* vc,
