@@ -306,8 +306,26 @@ int copy_in(gprx_ctx* c, void* dst, const void* src, size_t bytes, int mem) {
 
 // Recursive Cholesky + inverse over tile range [o, o+n) (tile units), all slots in lock step.
 // upd: the node lies in the trailing block of an ancestor (its tiles were updated into S); the top
-// child inherits the parent's flag, the bottom child follows the parent's SYRK
+// child inherits the parent's flag, the bottom child follows the parent's SYRK.
+// The right-hand side goes with it by forward substitution over the blocks (nodes of <= BLK_TILES
+// tiles, blk_range).  On entry Yw (yw_slot: the alpha buffer, free until k_alpha) is due to hold,
+// for the node's rows, y - L[rows, :64 o] z[:64 o]; on return db.z holds the node's final z.  A
+// block forms its Yw from the partials the TRSMs of its split ancestors left in zp (k_rhs), factors
+// as before with every L^-1 producer writing its partial of Linv Yw, and sums those into z
+// (k_znode); a split node's TRSM writes -L21 z1 for its bottom child, and its LINV21 the alpha
+// partial Linv21^T z2 (gemm_tile).
+void factor_block(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, int upd);
 void factor_rec(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, int upd) {
+  if (n > gprx::BLK_TILES) {
+    factor_block(c, st, db, o, n, upd);  // splits: n exceeds every leaf
+    return;
+  }
+  const double Bd = db.B, rows = n * TS;
+  timed(c, st, "alpha", Bd * rows * 2.0 * o, Bd * 8.0 * rows * (2.0 * o + 2.0), [&] { gprx::launch_rhs(db, o, n, st); });
+  factor_block(c, st, db, o, n, upd);
+  timed(c, st, "alpha", Bd * rows * (n + 1.0), Bd * 8.0 * rows * (n + 2.0), [&] { gprx::launch_znode(db, o, n, st); });
+}
+void factor_block(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, int upd) {
   const double T = TS, Bd = db.B;
   const int leaf = c->leaf_tiles > 0 ? c->leaf_tiles : (db.B >= 32 ? 4 : 1);
   if (n > 1 && n <= leaf) {
@@ -333,7 +351,8 @@ void factor_rec(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, i
   }
   const int h = n / 2;
   const double m1 = h * T, m2 = (n - h) * T;
-  factor_rec(c, st, db, o, h, upd);
+  const auto child = n > gprx::BLK_TILES ? factor_rec : factor_block;  // inside a block: no further blocks
+  child(c, st, db, o, h, upd);
   gprx::GemmGeom g{gprx::OP_TRSM, o, h, n, upd};
   const double f_trsm = Bd * m2 * m1 * m1, f_syrk = Bd * m2 * m2 * m1, f_tt = Bd * m2 * m1 * m1,
                f_linv = Bd * m1 * m2 * m2;
@@ -343,7 +362,7 @@ void factor_rec(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n, i
   gprx::GemmGeom gs{gprx::OP_SYRK, o, h, n, upd}, gt{gprx::OP_TT, o, h, n, upd};
   // T^T = L11^-T L21^T needs only rec(A11) and the TRSM: it runs in the SYRK's launch
   timed(c, st, "syrk_tt", f_syrk + f_tt, b_syrk + b_tt, [&] { gprx::launch_gemm(db, gs, st, gt); }, n);
-  factor_rec(c, st, db, o + h, n - h, 1);
+  child(c, st, db, o + h, n - h, 1);
   g.op = gprx::OP_LINV21;
   timed(c, st, "trtri_linv21", f_linv, b_linv, [&] { gprx::launch_gemm(db, g, st); }, n);
 }
@@ -372,12 +391,18 @@ void predict_group(gprx_ctx* c, hipStream_t st, const DevBatch& db) {
 
 // Whole evaluation of a batch (or a slot range of it) on stream `st`.
 void eval_group(gprx_ctx* c, hipStream_t st, const DevBatch& db, bool want_grad, bool want_pred) {
-  const double Bd = db.B, nt = db.nt, Np = db.Npad, d = db.d;
+  const double Bd = db.B, Np = db.Npad, d = db.d;
   timed(c, st, "gram", Bd * 3.0 * db.N * (double)db.N * d / 2.0, Bd * 8.0 * (Np * Np / 2.0 + Np * d),
         [&] { gprx::launch_gram(db, st); });
   factor_rec(c, st, db, 0, db.nt, 0);
-  timed(c, st, "alpha", Bd * Np * nt, Bd * 8.0 * Np * nt, [&] { gprx::launch_alpha(db, st, 0); });
-  timed(c, st, "alpha", Bd * Np * Np, Bd * 8.0 * Np * Np / 2.0, [&] { gprx::launch_alpha(db, st, 1); });
+  // k_alpha streams Mt's upper triangle inside each block and adds the ap rows below it
+  double tri = 0.0, apn = 0.0;  // elements per slot
+  for (int i = 0, lo, hi; i < db.nt; ++i) {
+    gprx::blk_range(db.nt, i, lo, hi);
+    tri += (double)TS * TS * (hi - i);
+    apn += (double)TS * (db.nt - hi);
+  }
+  timed(c, st, "alpha", Bd * (2.0 * tri + apn), Bd * 8.0 * (tri + apn + 2.0 * Np), [&] { gprx::launch_alpha(db, st); });
   if (want_grad)
     timed(c, st, "lauum_grad", Bd * (Np * Np * Np / 3.0 + Np * Np * d + 4.0 * Np * Np),
           Bd * 8.0 * (Np * Np + Np * (db.xs + 2.0)),  // minimum: Mt upper, Kf lower, Xc, alpha once

@@ -235,16 +235,25 @@ __device__ __forceinline__ double row_bcast16(double v, int m) {
   }
 }
 
-// per-tile partials of z = L^-1 y (see zp_acc4)
+// per-tile partials of z = L^-1 y and of the blocks' right-hand sides (see zp_acc4)
 __device__ __forceinline__ double* zp_row(const DevBatch& db, int slot, int h) {
   return db.zp + ((size_t)slot * 2 * db.nt + h) * db.Npad;
 }
+// per-row-tile partials of alpha = L^-T z (see ap_acc4): ap_row(ti)[64 tj + c] for tj left of ti's
+// block.  They live in zp's unused triangle, row 2 ti: of zp_row(2 c) the z partials use the
+// columns of the row tiles r >= c only, and tj < ti.  No buffer of their own: gprx_batch_bytes and
+// the allocation stay what they were.
+__device__ __forceinline__ double* ap_row(const DevBatch& db, int slot, int ti) { return zp_row(db, slot, 2 * ti); }
+// A block's working right-hand side Yw (k_rhs; DESIGN.md section 4, "Recursion") lives in the alpha
+// buffer: alpha is written last, by k_alpha, in stream order after every reader of Yw, and k_rhs
+// rewrites Yw before a block reads it, so neither sees the other.
+__device__ __forceinline__ double* yw_slot(const DevBatch& db, int slot) { return db.alpha + (size_t)slot * db.Npad; }
 // a diagonal tile from an LDS image: row r of X at img[r * rs + c * cs].  The 256-thread
 // workgroup splits the 64 columns in 4 quarters through the [256]-double scratch (no serial
 // chain); call from every thread of the workgroup (contains barriers).
 __device__ __forceinline__ void zp_diag(const DevBatch& db, int slot, int jt, const double* img, int rs, int cs,
                                         double* scr) {
-  const double* y = db.Y + (size_t)slot * db.Npad + jt * TS;
+  const double* y = yw_slot(db, slot) + jt * TS;
   const int r = threadIdx.x & 63, qc = threadIdx.x >> 6;
   double t = 0.0;
 #pragma unroll

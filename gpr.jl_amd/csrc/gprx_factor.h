@@ -112,7 +112,7 @@ __device__ __forceinline__ void leaf_body(const DevBatch& db, int o, int n, int 
       mma_64x16_ldsb(acc, Li + (size_t)ti * TS * ld + ti * TS, ld, tb);
       __builtin_amdgcn_wave_barrier();  // the reads of X precede accq_store_t's writes to tb
       if (n <= 4) {  // this quarter's z partial, from the registers: sum_c Linv[r][cq + c] y[cq + c]
-        const double* yq = db.Y + (size_t)slot * db.Npad + tj * TS + cq;
+        const double* yq = yw_slot(db, slot) + tj * TS + cq;
         double yv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) yv[q] = yq[lk + 4 * q];
@@ -161,7 +161,7 @@ __device__ __forceinline__ void leaf_body(const DevBatch& db, int o, int n, int 
           if (k < k0 || k >= k0 + 16) continue;
           const int tj = o + t, ti = tj + s;
           const double* Lt = Li + (size_t)(tj * TS) * ld + ti * TS;
-          const double* y = db.Y + (size_t)slot * db.Npad + tj * TS;
+          const double* y = yw_slot(db, slot) + tj * TS;
           double acc = 0.0;
 #pragma unroll
           for (int c = 16 * qc; c < 16 * qc + 16; ++c) acc = fma(Lt[(size_t)c * ld + r], y[c], acc);
@@ -518,7 +518,7 @@ __device__ __forceinline__ void leaf9_body(const DevBatch& db, int o, int upd) {
   double* Lw = db.Lw + so;
   double* Li = db.Linv + so;
   double* Mt = db.Mt + so;
-  const double* Y = db.Y + (size_t)slot * db.Npad;
+  const double* Y = yw_slot(db, slot);
   {  // tile o into wave 0's image (all eight waves, all loads in flight first)
     const double* A = K0 + (size_t)o * TS * ld + o * TS;
     double v[TS * TS / (2 * NTHR)];
@@ -979,7 +979,7 @@ __device__ __forceinline__ void leaf4_body(const DevBatch& db, int o, int upd, i
   double* Lw = db.Lw + so;
   double* Li = db.Linv + so;
   double* Mt = db.Mt + so;
-  const double* Y = db.Y + (size_t)slot * db.Npad;
+  const double* Y = yw_slot(db, slot);
   // z partial quarters in S's upper tile (o, o + 3): column 4 kz + c (off-diagonal tile kz), 24 +
   // 4 t + c (diagonal tile t), row r
   double* zg = S + (size_t)(o + 3) * TS * ld + o * TS;

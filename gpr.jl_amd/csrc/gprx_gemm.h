@@ -11,20 +11,39 @@
 
 namespace gprx {
 
-// z = L^-1 y fused into the producers of L^-1: every L^-1 tile (ti, tj) (written exactly once, by
-// a diagonal kernel, the leaf or LINV21) also writes its 64-row partial  L^-1[ti,tj] y[tj]  into
+// z = L^-1 y by forward substitution over the blocks (blk_range), fused into the producers of the
+// tiles.  Inside a block every L^-1 tile (ti, tj) (written exactly once, by a diagonal kernel, the
+// leaf or LINV21) also writes its 64-row partial  L^-1[ti,tj] Yw[tj]  into
 // zp[slot][2 tj + half][ti*64 + r] (half: 32-column halves of the pair-unit GEMM; 64-column
-// producers write half 0 and zero half 1).  k_alpha phase 0 then sums <= 2(ti+1) partials per row
-// instead of re-reading L^-1 from HBM.
-// 64 x 64 accumulator tile (mma_64x64 layout) of sgn * L^-1[ti,tj]
-__device__ __forceinline__ void zp_acc4(const DevBatch& db, int slot, int ti, int tj, const d4 (&acc)[QM][QN], double sgn) {
-  const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
-  const double* y = db.Y + (size_t)slot * db.Npad + tj * TS;
-  double yv[QN][4];
+// producers write half 0 and zero half 1).  Left of a block the same rows hold  -L[ti,tj] z[tj],
+// written by the TRSM of the split node that owns tile (ti, tj): k_rhs sums them into the block's
+// right-hand side Yw, and k_znode sums the block's own partials into z, <= 16 per row.
+// 64 x 64 accumulator tile (mma_64x64 layout) of sgn * M[ti,tj] times yv, the lane's 16 elements
+// of a 64-vector: loaded here (zp_load4), or spread from the lanes (zl_spread4).  The TRSM tile of
+// a split node loads its 64 elements of z one per lane AHEAD of the K loop (gemm_tile): loads and
+// stores retire through one in-order counter, so z loaded after the tile's 64 stores waits for all
+// of them.  Measured at B = 240, N = 2048, same-box pairs against the build without the epilogue:
+// potrf_trsm + 0.09 ms per step with the loads last, + 0.055 just before the stores, + 0.035 ahead
+// of the K loop.  LINV21's four z loads stay after its stores, as its z partial's loads always
+// were: ahead of the stores or of the K loop trtri_linv21 measured 0.05 ms slower, after them equal.
+__device__ __forceinline__ void zp_load4(const double* vec, int tj, double (&yv)[QN][4]) {  // vec: the slot's
+  const int lk = (threadIdx.x & 63) >> 4;
+  const double* y = vec + tj * TS;
 #pragma unroll
   for (int b = 0; b < QN; ++b)
 #pragma unroll
     for (int q = 0; q < 4; ++q) yv[b][q] = y[16 * b + lk + 4 * q];
+}
+__device__ __forceinline__ void zl_spread4(double zl, double (&yv)[QN][4]) {  // zl: element l of the 64-vector
+  const int lk = (threadIdx.x & 63) >> 4;
+#pragma unroll
+  for (int b = 0; b < QN; ++b)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) yv[b][q] = __shfl(zl, 16 * b + lk + 4 * q);
+}
+__device__ __forceinline__ void zp_acc4(const DevBatch& db, int slot, int ti, int tj, const d4 (&acc)[QM][QN],
+                                        const double (&yv)[QN][4], double sgn) {
+  const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
   double* z0 = zp_row(db, slot, 2 * tj) + ti * TS;
   double* z1 = zp_row(db, slot, 2 * tj + 1) + ti * TS;
 #pragma unroll
@@ -40,6 +59,28 @@ __device__ __forceinline__ void zp_acc4(const DevBatch& db, int slot, int ti, in
       z1[16 * a + lr] = 0.0;
     }
   }
+}
+// alpha = L^-T z across blocks: the LINV21 tile (ti, tj) of a split node, still in the accumulators
+// (mma_64x64 layout), writes  L^-1[ti,tj]^T z[ti]  (z of the bottom child is final by then) into
+// ap[slot][ti][tj*64 + c]; k_alpha adds the rows ti >= blk_hi to what it streams of Mt inside the
+// block.  The 16 lanes' sums by DPP, as the prediction variance's epilogue in gemm_tile.
+__device__ __forceinline__ void ap_acc4(const DevBatch& db, int slot, int ti, int tj, const d4 (&acc)[QM][QN]) {
+  const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
+  const double* z = db.z + (size_t)slot * db.Npad + ti * TS;
+  double zv[QM];
+#pragma unroll
+  for (int a = 0; a < QM; ++a) zv[a] = z[16 * a + lr];
+  double* ap = ap_row(db, slot, ti) + tj * TS;
+#pragma unroll
+  for (int b = 0; b < QN; ++b)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double v = 0.0;
+#pragma unroll
+      for (int a = 0; a < QM; ++a) v = fma(acc[a][b][q], zv[a], v);
+      v = row_sum16(v);
+      if (lr == 0) ap[16 * b + lk + 4 * q] = v;
+    }
 }
 // Units of the 4-wave workgroups of k_gemm / k_lauum_grad: UR x UC output tiles (UR UC = 4), wave w
 // = tile (pr + w / UC, pc + w % UC).  The shape follows the op so that the four waves of a unit
@@ -142,6 +183,11 @@ __device__ __forceinline__ void gemm_tile(const DevBatch& db, const GemmGeom& g,
   }
   const double* Ak = to.A;
   const double* Bk = to.B;
+  // a split node's TRSM tile (the REV_B instance): the lane's element of z[tj] (final: the top
+  // child returned), in flight under the K loop (see zp_load4)
+  const bool split = !PV && g.n > BLK_TILES;
+  double zl = 0.0;
+  if (PM == REV_B && split && op == OP_TRSM) zl = db.z[(size_t)slot * db.Npad + tj * TS + l];
   if constexpr (PV) {  // prediction (own kernel instance): skip the last test tile's all-padding blocks
     const int nbv = __builtin_amdgcn_readfirstlane((db.M - tj * TS + 15) >> 4);
     if (nbv >= QN) mma_64x64(acc, Ak, ld, Bk, ldb, to.Kn);
@@ -199,6 +245,9 @@ __device__ __forceinline__ void gemm_tile(const DevBatch& db, const GemmGeom& g,
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[a][b][q] = neg_f64(acc[a][b][q]);
   }
+  // wave-uniform: a split node's TRSM hands -L21 z to the bottom child's blocks, its LINV21 forms
+  // the alpha partial; inside a block LINV21 writes its z partial as every producer
+  double yv[QN][4];
   const __amdgpu_buffer_rsrc_t crw = buffer_rsrc(Cm + (size_t)(tj * TS) * ld + ti * TS, 0x7ffffff0);
 #pragma unroll
   for (int a = 0; a < QM; ++a)
@@ -206,7 +255,19 @@ __device__ __forceinline__ void gemm_tile(const DevBatch& db, const GemmGeom& g,
     for (int b = 0; b < QN; ++b)
 #pragma unroll
       for (int q = 0; q < 4; ++q) buffer_store_f64(crw, vl + 128 * a, (16 * b + 4 * q) * Lb, acc[a][b][q]);
-  if (op == OP_LINV21) zp_acc4(db, slot, ti, tj, acc, 1.0);
+  if (op == OP_TRSM && split) {
+    if (PM == REV_B) zl_spread4(zl, yv);
+    else zp_load4(db.z + (size_t)slot * db.Npad, tj, yv);
+    zp_acc4(db, slot, ti, tj, acc, yv, -1.0);
+  }
+  if (op == OP_LINV21) {
+    if (split) {
+      ap_acc4(db, slot, ti, tj, acc);
+    } else {
+      zp_load4(yw_slot(db, slot), tj, yv);
+      zp_acc4(db, slot, ti, tj, acc, yv, 1.0);
+    }
+  }
   if (op != OP_LINV21) GTS(g, pass, 3);
   if (op == OP_LINV21) {  // Mt[tj, ti] = Linv[ti, tj]^T, transposed through LDS 32 rows at a time
     // (round 5: two rounds instead of four 16-row ones, and 16-B reads and stores: every store
@@ -362,11 +423,11 @@ __device__ __forceinline__ void gemm_body(const DevBatch& db, const GemmGeom& g1
   gemm_unit<PV, PM>(db, g1, g2, slot, u, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), T1);
 }
 
-// 64 x 32 accumulator half-tile (mma_64x32_s1 layout, columns 32 half ..) of sgn * L^-1[ti,tj]
-__device__ __forceinline__ void zp_acc2(const DevBatch& db, int slot, int ti, int tj, int half, const d4 (&acc)[WM][WN],
-                                        double sgn) {
+// 64 x 32 accumulator half-tile (mma_64x32_s1 layout, columns 32 half ..) of sgn * M[ti,tj]; vec: the slot's Yw or z
+__device__ __forceinline__ void zp_acc2(const DevBatch& db, const double* vec, int slot, int ti, int tj, int half,
+                                        const d4 (&acc)[WM][WN], double sgn) {
   const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
-  const double* y = db.Y + (size_t)slot * db.Npad + tj * TS + 32 * half;
+  const double* y = vec + tj * TS + 32 * half;
   double yv[WN][4];
 #pragma unroll
   for (int b = 0; b < WN; ++b)
@@ -383,6 +444,30 @@ __device__ __forceinline__ void zp_acc2(const DevBatch& db, int slot, int ti, in
     t = sum_xor32(sum_xor16(t));
     if (lk == 0) z[16 * a + lr] = sgn * t;
   }
+}
+// ap_acc4 for the half-tile
+__device__ __forceinline__ void ap_acc2(const DevBatch& db, int slot, int ti, int tj, int half, const d4 (&acc)[WM][WN],
+                                        double sgn) {
+  // the lane's indices are formed here, after the K loop: hoisted above it (k_gemm_p runs at 128
+  // VGPRs) they would be one more value spilled across it
+  int l = threadIdx.x & 63;
+  asm volatile("" : "+v"(l));
+  const int lr = l & 15, lk = l >> 4;
+  const double* z = db.z + (size_t)slot * db.Npad + ti * TS;
+  double zv[WM];
+#pragma unroll
+  for (int a = 0; a < WM; ++a) zv[a] = z[16 * a + lr];
+  double* ap = ap_row(db, slot, ti) + tj * TS + 32 * half;
+#pragma unroll
+  for (int b = 0; b < WN; ++b)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double v = 0.0;
+#pragma unroll
+      for (int a = 0; a < WM; ++a) v = fma(acc[a][b][q], zv[a], v);
+      v = row_sum16(v);
+      if (lr == 0) ap[16 * b + lk + 4 * q] = sgn * v;
+    }
 }
 // Small recursion nodes: unit = 2 vertically adjacent 64 x 64 tiles, wave = 64 x 32, single-stage
 // core at 4 waves/SIMD (more, shorter units than the 2 x 2 form: better for K <= 512).
@@ -507,7 +592,6 @@ __device__ __forceinline__ void gemm_tile_pair(const DevBatch& db, const GemmGeo
 #pragma unroll
         for (int q = 0; q < 4; ++q) Ct[(size_t)(16 * b + lk + 4 * q) * ld + 16 * a + lr] = sgn * acc[a][b][q];
   }
-  if (op == OP_LINV21) zp_acc2(db, slot, ti, tj, wc, acc, -1.0);
   if (op == OP_LINV21) {  // Mt[tj, ti] = Linv[ti, tj]^T (direct: an LDS transpose measured slower here)
     double* Mtt = db.Mt + so + (size_t)(ti * TS) * ld + tj * TS + 32 * wc;
 #pragma unroll
@@ -517,6 +601,10 @@ __device__ __forceinline__ void gemm_tile_pair(const DevBatch& db, const GemmGeo
 #pragma unroll
         for (int q = 0; q < 4; ++q) Mtt[(size_t)(16 * a + lr) * ld + 16 * b + lk + 4 * q] = -acc[a][b][q];
   }
+  const bool split = g.n > BLK_TILES;  // as gemm_tile, last: nothing else is live; one call site of zp_acc2 (inlined once)
+  if (op == OP_LINV21 && split) ap_acc2(db, slot, ti, tj, wc, acc, -1.0);
+  else if (op == OP_LINV21 || (op == OP_TRSM && split))
+    zp_acc2(db, op == OP_TRSM ? db.z + (size_t)slot * db.Npad : yw_slot(db, slot), slot, ti, tj, wc, acc, -1.0);
 }
 
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_gemm_p(DevBatch db, GemmGeom g, GemmGeom g2) {

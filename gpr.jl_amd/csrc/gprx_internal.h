@@ -48,8 +48,10 @@ struct DevBatch {
   double* Linv;                // B x mat
   double* Mt;                  // B x mat
   double* z;                   // B x Npad        z = L^{-1} y
-  double* zp;                  // B x 2nt x Npad  per-tile partials of z (see zp_acc4)
-  double* alpha;               // B x Npad        alpha = K^{-1} y
+  double* zp;                  // B x 2nt x Npad  per-tile partials of z (see zp_acc4); its unused triangle
+                               //                 holds the partials of alpha (ap_row)
+  double* alpha;               // B x Npad        alpha = K^{-1} y; until k_alpha writes it, a block's
+                               //                 working right-hand side (yw_slot)
   double* params;              // B x pst: [0,d) il2 = exp(-2 log ell), d: sf2, d+1: noise diag
                                //          (sn2 + eps), d+2: sn2
   double* theta;               // B x (d+2) hyper-parameters [log sn, log ell_1..d, log sf] of the
@@ -96,6 +98,27 @@ __host__ __device__ inline void op_rect(const GemmGeom& g, int nt, int mt, int& 
     case OP_PREDVAR: r0 = 0; c0 = 0; R = nt; C = mt; break;
     default: r0 = c0 = R = C = 0; break;
   }
+}
+
+// Blocks of the recursion: factor_rec (gprx_api.hip) halves a node of more than BLK_TILES tiles (a
+// split node) and finishes a smaller one as a block, by whichever kernels.  z is formed by forward
+// substitution over the blocks and alpha's products across blocks come from the split nodes' LINV21
+// tiles, so the host and the kernels share this one splitting rule.
+constexpr int BLK_TILES = 8;
+// the block [lo, hi) of tile i among nt tiles
+__host__ __device__ inline void blk_range(int nt, int i, int& lo, int& hi) {
+  int o = 0, n = nt;
+  while (n > BLK_TILES) {
+    const int h = n / 2;
+    if (i < o + h) {
+      n = h;
+    } else {
+      o += h;
+      n -= h;
+    }
+  }
+  lo = o;
+  hi = o + n;
 }
 
 // Minimal-coordinate rollout (k_rollout): one GP of a rollout group, read from a batch slot after
@@ -261,7 +284,10 @@ void launch_leaf(const DevBatch& b, int o, int n, int upd, hipStream_t s);
 void launch_node8(const DevBatch& b, int o, int upd, hipStream_t s, bool four = false);  // a whole 8-tile node (k_node8)
 // one launch; with g2.op != OP_NONE the units of g2 are appended to g's (independent ops)
 void launch_gemm(const DevBatch& b, const GemmGeom& g, hipStream_t s, const GemmGeom& g2 = GemmGeom{OP_NONE, 0, 0, 0});
-void launch_alpha(const DevBatch& b, hipStream_t s, int phase);
+// around a block [o, o + n): its right-hand side Yw before it, its rows of z after it
+void launch_rhs(const DevBatch& b, int o, int n, hipStream_t s);
+void launch_znode(const DevBatch& b, int o, int n, hipStream_t s);
+void launch_alpha(const DevBatch& b, hipStream_t s);
 void launch_lauum_grad(const DevBatch& b, hipStream_t s);
 // k_lauum_grad's job table: units of 4 output tiles, folded in pairs; LU ints per unit (see
 // lauum_plan in gprx_kernels.hip).  Returns the jobs per slot; *nunits the units, *nimg the

@@ -396,29 +396,65 @@ __device__ __forceinline__ void diag_store(const DevBatch& db, int slot, int jt,
 namespace gprx {
 
 // ============================================================================================
-// alpha = L^-T (L^-1 y).  phase 0: z = Linv y ; phase 1: alpha = Mt z.   grid = B * nt
+// z = L^-1 y by forward substitution over the blocks, alpha = L^-T z.  Around every block [lo, lo + n)
+// of the recursion (blk_range; factor_rec launches them):
+//   k_rhs   : Yw = y + sum_{h < 2 lo} zp_row(h), the partials -L[i,tj] z[tj] the split nodes' TRSMs
+//             wrote left of the block.  The first block's is a copy of y, launched all the same:
+//             Yw carries nothing from one evaluation to the next.                      grid = B * n
+//   k_znode : z = sum_{h = 2 lo}^{2(i+1)-1} zp_row(h), the block's own partials.          grid = B * n
+// and once per evaluation
+//   k_alpha : alpha = Mt z inside each block + the split nodes' LINV21 partials ap.     grid = B * nt
+// The partials are summed in a fixed order: thread group pt takes every fourth row, then the four
+// groups' sums in order.
 // ============================================================================================
-__global__ __launch_bounds__(NTHR) void k_alpha(DevBatch db, int phase) {
+__device__ __forceinline__ double zp_sum(const DevBatch& db, int slot, int i, int h0, int h1, double (&part)[4][TS]) {
+  const int r = threadIdx.x & 63, pt = threadIdx.x >> 6;
+  double acc = 0.0;
+  for (int h = h0 + pt; h < h1; h += 4) acc += zp_row(db, slot, h)[i * TS + r];
+  part[pt][r] = acc;
+  __syncthreads();
+  return ((part[0][r] + part[1][r]) + part[2][r]) + part[3][r];
+}
+__global__ __launch_bounds__(NTHR) void k_rhs(DevBatch db, int lo, int n) {
+  __shared__ double part[4][TS];
+  int slot, u;
+  if (!map_slot(db, n, slot, u)) return;
+  const int i = lo + u, r = threadIdx.x & 63;
+  const double s = zp_sum(db, slot, i, 0, 2 * lo, part);
+  const size_t e = (size_t)slot * db.Npad + i * TS + r;
+  if (threadIdx.x < TS) yw_slot(db, slot)[i * TS + r] = lo ? db.Y[e] + s : db.Y[e];
+}
+__global__ __launch_bounds__(NTHR) void k_znode(DevBatch db, int lo, int n) {
+  __shared__ double part[4][TS];
+  int slot, u;
+  if (!map_slot(db, n, slot, u)) return;
+  const int i = lo + u, r = threadIdx.x & 63;
+  const double s = zp_sum(db, slot, i, 2 * lo, 2 * (i + 1), part);
+  if (threadIdx.x < TS) db.z[(size_t)slot * db.Npad + i * TS + r] = s;
+}
+__global__ __launch_bounds__(NTHR) void k_alpha(DevBatch db) {
   __shared__ double part[4][TS];
   int slot, i;
   if (!map_slot(db, db.nt, slot, i)) return;
   const int r = threadIdx.x & 63, pt = threadIdx.x >> 6;
-  if (phase == 0) {  // z = L^-1 y from the producers' partials: rows of tile i, halves h < 2(i+1)
-    double acc = 0.0;
-    for (int h = pt; h < 2 * (i + 1); h += 4) acc += zp_row(db, slot, h)[i * TS + r];
-    part[pt][r] = acc;
-    __syncthreads();
-    if (pt == 0) db.z[(size_t)slot * db.Npad + i * TS + r] = ((part[0][r] + part[1][r]) + part[2][r]) + part[3][r];
-    return;
+  int blo, bhi;
+  blk_range(db.nt, i, blo, bhi);
+  // the partials from below the block first: their loads are in flight under the Mt stream
+  __shared__ double apart[4][TS];
+  {
+    double a = 0.0;
+    for (int ti = bhi + pt; ti < db.nt; ti += 4) a += ap_row(db, slot, ti)[i * TS + r];
+    apart[pt][r] = a;
   }
   const size_t ld = db.ld;
   // lane: rows 2 rp, 2 rp + 1 of the tile row (one 16-B load), columns of parity cp: one load
-  // instruction reads two whole 512-B column segments.  The column range [k0, Npad) is split in 4
-  // contiguous quarters of whole 16-column groups (wave-uniform, so z comes in by scalar loads).
+  // instruction reads two whole 512-B column segments.  The column range [k0, end of the block) is
+  // split in 4 contiguous quarters of whole 16-column groups (wave-uniform, so z comes in by scalar
+  // loads).
   const int rp = r & 31, cp = r >> 5, w = __builtin_amdgcn_readfirstlane(pt);
   const double* A = db.Mt + (size_t)slot * db.mat + i * TS + 2 * rp + (size_t)cp * ld;
   const double* v = db.z + (size_t)slot * db.Npad;
-  const int k0 = i * TS, k1 = db.Npad;
+  const int k0 = i * TS, k1 = bhi * TS;
   const int ng = (k1 - k0) / 16, g0 = (ng * w) / 4, g1 = (ng * (w + 1)) / 4;
   typedef double d2 __attribute__((ext_vector_type(2)));
   d2 acc[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
@@ -453,7 +489,8 @@ __global__ __launch_bounds__(NTHR) void k_alpha(DevBatch db, int phase) {
   }
   __syncthreads();
   if (pt == 0) {
-    const double s = ((part[0][r] + part[1][r]) + part[2][r]) + part[3][r];
+    double s = ((part[0][r] + part[1][r]) + part[2][r]) + part[3][r];
+    if (bhi < db.nt) s += ((apart[0][r] + apart[1][r]) + apart[2][r]) + apart[3][r];
     db.alpha[(size_t)slot * db.Npad + i * TS + r] = s;
   }
 }
@@ -1130,8 +1167,14 @@ void launch_gemm(const DevBatch& b, const GemmGeom& g, hipStream_t s, const Gemm
   else if (g.op == OP_LINV21) hipLaunchKernelGGL(k_gemm<REV_A>, dim3(grid_blocks(b.B, T)), dim3(NTHR), lds, s, b, g, g2);
   else hipLaunchKernelGGL(k_gemm<TRI_A_FIRST>, dim3(grid_blocks(b.B, T)), dim3(NTHR), lds, s, b, g, g2);
 }
-void launch_alpha(const DevBatch& b, hipStream_t s, int phase) {
-  hipLaunchKernelGGL(k_alpha, dim3(grid_blocks(b.B, b.nt)), dim3(NTHR), 0, s, b, phase);
+void launch_rhs(const DevBatch& b, int o, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_rhs, dim3(grid_blocks(b.B, n)), dim3(NTHR), 0, s, b, o, n);
+}
+void launch_znode(const DevBatch& b, int o, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_znode, dim3(grid_blocks(b.B, n)), dim3(NTHR), 0, s, b, o, n);
+}
+void launch_alpha(const DevBatch& b, hipStream_t s) {
+  hipLaunchKernelGGL(k_alpha, dim3(grid_blocks(b.B, b.nt)), dim3(NTHR), 0, s, b);
 }
 void launch_lauum_grad(const DevBatch& b, hipStream_t s) {
   hipLaunchKernelGGL(k_lauum_grad, dim3(grid_blocks(b.B, b.nlj)), dim3(NTHR), lauum_lds(b), s, b);
