@@ -1301,60 +1301,6 @@ static int rollout_gps(gprx_ctx* c, const std::string& fn, int ngroups, int G, g
   return GPRX_OK;
 }
 
-// ---- rollout in minimal coordinates ------------------------------------------------------------
-int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, int ngroups,
-                     gprx_batch* const* batches, const int* slots, int T, const int* traj_group,
-                     const double* start, double* final_state) {
-  if (!c) return GPRX_INVALID_ARGUMENT;
-  if (mech < GPRX_MECH_P1 || mech > GPRX_MECH_FB || steps < 0 || ngroups < 1 || T < 0 || !std::isfinite(dt))
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min: bad mechanism / steps / groups / dt");
-  if (T == 0) return GPRX_OK;
-  if (!batches || !slots || !traj_group || !start || !final_state)
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min: null argument");
-  // coordinates (q, qdot) per mechanism: P1 theta; P2 theta1, theta2 (relative); CP x, theta;
-  // FB theta1, theta3 -- the angle coordinates get (sin, cos) features when usesin
-  const int nc = mech == GPRX_MECH_P1 ? 1 : 2;
-  const int ang0 = mech == GPRX_MECH_CP ? 0 : 1, ang1 = nc > 1 ? 1 : 0;
-  const int dobs = (usesin && ang0 ? 3 : 2) + (nc > 1 ? (usesin && ang1 ? 3 : 2) : 0);
-  std::lock_guard<std::mutex> g(c->mu);
-  std::vector<gprx::RolloutGP> gps;
-  double np = 0.0;
-  int rc = rollout_gps(c, "gprx_rollout_min", ngroups, nc, batches, slots, dobs,
-                       std::to_string(dobs) + " for this mechanism / usesin", T, traj_group, gps, &np);
-  if (rc) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  // one device buffer: [gps | group | start | out]
-  const size_t sw = (size_t)T * 2 * nc * sizeof(double);
-  Layout l;
-  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
-               o_out = l.take<char>(sw);
-  char* base;
-  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
-  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
-  gprx::RolloutArgs a{};
-  a.gps = at<gprx::RolloutGP>(base, o_gps);
-  a.group = at<int>(base, o_grp);
-  a.start = at<double>(base, o_st);
-  a.out = at<double>(base, o_out);
-  a.T = T;
-  a.nc = nc;
-  a.d = dobs;
-  a.steps = steps;
-  a.usesin = usesin ? 1 : 0;
-  a.ang0 = ang0;
-  a.ang1 = ang1;
-  a.dt = dt;
-  timed(c, c->stream, "rollout", np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0,
-        [&] { gprx::launch_rollout(a, c->dist_mode, c->stream); });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  collect(c);
-  return GPRX_OK;
-}
-
 // ---- maximal-coordinate physics -----------------------------------------------------------------
 // The experiment mechanisms' joints (examples/utils/data/simulations.jl; oracle/projection_oracle.py
 // mechanism()): sub-joints in the order of the equality constraints and their rows.
@@ -1498,6 +1444,53 @@ int newton_call(gprx_ctx* c, const char* name, int mech, double dt, int T, const
   return GPRX_OK;
 }
 
+// What the rollout calls share around their launch: one device buffer [gps | group | start | out |
+// the per-trajectory outputs `extra`, in their order] with its three uploads, and after the launch
+// the copies back -- out, then every extra output the caller wants -- with the synchronise.
+struct RolloutIo {
+  struct Extra {
+    void* host;   // where the caller wants the T values, or null
+    size_t elem;  // bytes per trajectory
+    size_t off;
+  };
+  char* base = nullptr;
+  size_t o_gps = 0, o_grp = 0, o_st = 0, o_out = 0, sw = 0;  // sw: bytes of start and of out
+  std::vector<Extra> extra;
+  template <class T>
+  T* dev(size_t k) const {
+    return at<T>(base, extra[k].off);
+  }
+};
+template <class Args>
+int rollout_upload(gprx_ctx* c, RolloutIo& io, const std::vector<gprx::RolloutGP>& gps, int T, const int* traj_group,
+                   const double* start, Args& a) {
+  Layout l;
+  io.o_gps = l.take<gprx::RolloutGP>(gps.size());
+  io.o_grp = l.take<int>(T);
+  io.o_st = l.take<char>(io.sw);
+  io.o_out = l.take<char>(io.sw);
+  for (RolloutIo::Extra& e : io.extra) e.off = l.take<char>((size_t)T * e.elem);
+  int rc = ctx_scratch(c, l.size, &io.base);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(io.base + io.o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(io.base + io.o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(io.base + io.o_st, start, io.sw, hipMemcpyHostToDevice, c->stream));
+  a.gps = at<gprx::RolloutGP>(io.base, io.o_gps);
+  a.group = at<int>(io.base, io.o_grp);
+  a.start = at<double>(io.base, io.o_st);
+  a.out = at<double>(io.base, io.o_out);
+  return GPRX_OK;
+}
+int rollout_download(gprx_ctx* c, const RolloutIo& io, int T, double* final_state) {
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(final_state, io.base + io.o_out, io.sw, hipMemcpyDeviceToHost, c->stream));
+  for (const RolloutIo::Extra& e : io.extra)
+    if (e.host) HIPCHK(c, hipMemcpyAsync(e.host, io.base + e.off, (size_t)T * e.elem, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  return GPRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1516,6 +1509,76 @@ int gprx_vi_step(gprx_ctx* c, int mech, double dt, int T, const double* cstates,
                                    [](gprx::ViArgs& a, const double*) { a.grav = 9.81; });  // |mechanism.g| (simulations.jl; gprx/vi.py GRAV)
 }
 
+// ---- rollout in minimal coordinates ------------------------------------------------------------
+// gprx_rollout_min (vi_regularizer null: MeanZero GPs, k_rollout<., RolloutArgs>) and
+// gprx_rollout_min_md (predictdynamicsmin with MeanDynamics GPs, examples/utils/predictdynamics.jl:
+// 30-102 with src/mDynamics.jl:41-55: the physics mean per step, k_rollout<., RolloutMinMdArgs>): one
+// validation, scratch layout and launch
+static int rollout_min_call(gprx_ctx* c, const std::string& fn, const char* stat, int mech, int usesin, double dt, int steps,
+                            const double* vi_regularizer, int ngroups, gprx_batch* const* batches, const int* slots, int T,
+                            const int* traj_group, const double* start, double* final_state, int* status, int* vi_status) {
+  if (!c) return GPRX_INVALID_ARGUMENT;
+  gprx::RolloutMinMdArgs a{};
+  // The MeanZero form accepts any finite dt, as it always has (dt only scales the updates); the
+  // physics step of the MeanDynamics form needs dt > 0, as gprx_vi_step does.
+  if (!build_mech(mech, a.mech) || steps < 0 || ngroups < 1 || T < 0 || !std::isfinite(dt) ||
+      (vi_regularizer && (!(dt > 0.0) || !std::isfinite(*vi_regularizer))))
+    return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / steps / groups / dt" + (vi_regularizer ? " / regularizer" : ""));
+  if (T == 0) return GPRX_OK;
+  if (!batches || !slots || !traj_group || !start || !final_state) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  // coordinates (q, qdot) per mechanism: P1 theta; P2 theta1, theta2 (relative); CP x, theta;
+  // FB theta1, theta3 -- the angle coordinates get (sin, cos) features when usesin
+  const int nc = mech == GPRX_MECH_P1 ? 1 : 2;
+  const int ang0 = mech == GPRX_MECH_CP ? 0 : 1, ang1 = nc > 1 ? 1 : 0;
+  const int dobs = (usesin && ang0 ? 3 : 2) + (nc > 1 ? (usesin && ang1 ? 3 : 2) : 0);
+  std::lock_guard<std::mutex> g(c->mu);
+  std::vector<gprx::RolloutGP> gps;
+  double np = 0.0;
+  int rc = rollout_gps(c, fn, ngroups, nc, batches, slots, dobs, std::to_string(dobs) + " for this mechanism / usesin", T,
+                       traj_group, gps, &np);
+  if (rc) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  RolloutIo io;
+  io.sw = (size_t)T * 2 * nc * sizeof(double);
+  io.extra = {{status, sizeof(int), 0}, {vi_status, sizeof(int), 0}};
+  if ((rc = rollout_upload(c, io, gps, T, traj_group, start, a))) return rc;
+  a.T = T;
+  a.nc = nc;
+  a.d = dobs;
+  a.steps = steps;
+  a.usesin = usesin ? 1 : 0;
+  a.ang0 = ang0;
+  a.ang1 = ang1;
+  a.dt = dt;
+  a.mech_id = mech;
+  // link lengths of the experiment mechanisms (examples/utils/simulations.jl; gprx/rollout.py LENGTHS)
+  a.len[0] = mech == GPRX_MECH_CP ? 0.5 : 1.0;
+  a.len[1] = 1.0;
+  a.status = io.dev<int>(0);
+  if (vi_regularizer)  // newton! as gprx_vi_step's callers run it (gprx/projection.py vi_step)
+    a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? io.dev<int>(1) : nullptr};
+  timed(c, c->stream, stat, np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0, [&] {
+    if (vi_regularizer) gprx::launch_rollout_min_md(a, c->dist_mode, c->stream);
+    else gprx::launch_rollout(a, c->dist_mode, c->stream);
+  });
+  return rollout_download(c, io, T, final_state);
+}
+
+int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, int ngroups,
+                     gprx_batch* const* batches, const int* slots, int T, const int* traj_group,
+                     const double* start, double* final_state) {
+  return rollout_min_call(c, "gprx_rollout_min", "rollout", mech, usesin, dt, steps, nullptr, ngroups, batches, slots, T,
+                          traj_group, start, final_state, nullptr, nullptr);
+}
+
+int gprx_rollout_min_md(gprx_ctx* c, int mech, int usesin, double dt, int steps, double vi_regularizer, int ngroups,
+                        gprx_batch* const* batches, const int* slots, int T, const int* traj_group, const double* start,
+                        double* final_state, int* status, int* vi_status) {
+  return rollout_min_call(c, "gprx_rollout_min_md", "rollout_min_md", mech, usesin, dt, steps, &vi_regularizer, ngroups, batches,
+                          slots, T, traj_group, start, final_state, status, vi_status);
+}
+
+// ---- rollout in maximal coordinates ------------------------------------------------------------
 // gprx_rollout_max (vi_regularizer null: MeanZero GPs, k_rollout_max) and gprx_rollout_max_md (the
 // physics mean per step, k_rollout_max<., RolloutMaxMdArgs>): one validation, scratch layout and launch
 static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat, int mech, double dt, int steps, double regularizer,
@@ -1545,15 +1608,10 @@ static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat
   int rc = rollout_gps(c, fn, ngroups, G, batches, slots, d, "13 nbodies", T, traj_group, gps, &np);
   if (rc) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  const size_t sw = (size_t)T * d * sizeof(double);
-  Layout l;
-  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
-               o_out = l.take<char>(sw), o_pe = l.take<double>(T), o_ss = l.take<int>(T), o_vs = l.take<int>(T);
-  char* base;
-  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
-  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
+  RolloutIo io;
+  io.sw = (size_t)T * d * sizeof(double);
+  io.extra = {{proj_err, sizeof(double), 0}, {status, sizeof(int), 0}, {vi_status, sizeof(int), 0}};
+  if ((rc = rollout_upload(c, io, gps, T, traj_group, start, a))) return rc;
   a.mech = M;
   a.dt = dt;
   a.reg = regularizer;
@@ -1563,27 +1621,15 @@ static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat
   a.T = T;
   a.G = G;
   a.d = d;
-  a.gps = at<gprx::RolloutGP>(base, o_gps);
-  a.group = at<int>(base, o_grp);
-  a.start = at<double>(base, o_st);
-  a.out = at<double>(base, o_out);
-  a.perr = at<double>(base, o_pe);
-  a.status = at<int>(base, o_ss);
+  a.perr = io.dev<double>(0);
+  a.status = io.dev<int>(1);
   if (vi_regularizer)  // newton! as gprx_vi_step's callers run it (gprx/projection.py vi_step)
-    a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? at<int>(base, o_vs) : nullptr};
+    a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? io.dev<int>(2) : nullptr};
   timed(c, c->stream, stat, np * steps * (3.0 * d + 24.0), np * steps * (d + 1) * 8.0, [&] {
     if (vi_regularizer) gprx::launch_rollout_max_md(a, c->dist_mode, c->stream);
     else gprx::launch_rollout_max(a, c->dist_mode, c->stream);
   });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
-  if (proj_err) HIPCHK(c, hipMemcpyAsync(proj_err, base + o_pe, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_ss, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (vi_regularizer && vi_status)
-    HIPCHK(c, hipMemcpyAsync(vi_status, base + o_vs, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  collect(c);
-  return GPRX_OK;
+  return rollout_download(c, io, T, final_state);
 }
 
 int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups,
@@ -1599,68 +1645,6 @@ int gprx_rollout_max_md(gprx_ctx* c, int mech, double dt, int steps, double regu
                         int* vi_status) {
   return rollout_max_call(c, "gprx_rollout_max_md", "rollout_max_md", mech, dt, steps, regularizer, &vi_regularizer, ngroups,
                           batches, slots, G, vw_idx1, T, traj_group, start, final_state, proj_err, status, vi_status);
-}
-
-// predictdynamicsmin with MeanDynamics GPs (examples/utils/predictdynamics.jl:30-102 with
-// src/mDynamics.jl:41-55): gprx_rollout_min's validation and layout, plus the physics step
-int gprx_rollout_min_md(gprx_ctx* c, int mech, int usesin, double dt, int steps, double vi_regularizer, int ngroups,
-                        gprx_batch* const* batches, const int* slots, int T, const int* traj_group, const double* start,
-                        double* final_state, int* status, int* vi_status) {
-  if (!c) return GPRX_INVALID_ARGUMENT;
-  gprx::RolloutMinMdArgs a{};
-  if (!build_mech(mech, a.mech) || steps < 0 || ngroups < 1 || T < 0 || !(dt > 0.0) || !std::isfinite(dt) ||
-      !std::isfinite(vi_regularizer))
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min_md: bad mechanism / steps / groups / dt / regularizer");
-  if (T == 0) return GPRX_OK;
-  if (!batches || !slots || !traj_group || !start || !final_state)
-    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_rollout_min_md: null argument");
-  const int nc = mech == GPRX_MECH_P1 ? 1 : 2;  // coordinates and features as gprx_rollout_min
-  const int ang0 = mech == GPRX_MECH_CP ? 0 : 1, ang1 = nc > 1 ? 1 : 0;
-  const int dobs = (usesin && ang0 ? 3 : 2) + (nc > 1 ? (usesin && ang1 ? 3 : 2) : 0);
-  std::lock_guard<std::mutex> g(c->mu);
-  std::vector<gprx::RolloutGP> gps;
-  double np = 0.0;
-  int rc = rollout_gps(c, "gprx_rollout_min_md", ngroups, nc, batches, slots, dobs,
-                       std::to_string(dobs) + " for this mechanism / usesin", T, traj_group, gps, &np);
-  if (rc) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
-  // one device buffer: [gps | group | start | out | status | vi_status]
-  const size_t sw = (size_t)T * 2 * nc * sizeof(double);
-  Layout l;
-  const size_t o_gps = l.take<gprx::RolloutGP>(gps.size()), o_grp = l.take<int>(T), o_st = l.take<char>(sw),
-               o_out = l.take<char>(sw), o_ss = l.take<int>(T), o_vs = l.take<int>(T);
-  char* base;
-  if ((rc = ctx_scratch(c, l.size, &base))) return rc;
-  HIPCHK(c, hipMemcpyAsync(base + o_gps, gps.data(), gps.size() * sizeof(gprx::RolloutGP), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_grp, traj_group, (size_t)T * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_st, start, sw, hipMemcpyHostToDevice, c->stream));
-  a.gps = at<gprx::RolloutGP>(base, o_gps);
-  a.group = at<int>(base, o_grp);
-  a.start = at<double>(base, o_st);
-  a.out = at<double>(base, o_out);
-  a.status = at<int>(base, o_ss);
-  a.T = T;
-  a.nc = nc;
-  a.d = dobs;
-  a.steps = steps;
-  a.mech_id = mech;
-  a.usesin = usesin ? 1 : 0;
-  a.ang0 = ang0;
-  a.ang1 = ang1;
-  a.dt = dt;
-  // link lengths of the experiment mechanisms (examples/utils/simulations.jl; gprx/rollout.py LENGTHS)
-  a.len[0] = mech == GPRX_MECH_CP ? 0.5 : 1.0;
-  a.len[1] = 1.0;
-  a.vi = gprx::RolloutViArgs{vi_regularizer, 1e-10, 9.81, 100, vi_status ? at<int>(base, o_vs) : nullptr};
-  timed(c, c->stream, "rollout_min_md", np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0,
-        [&] { gprx::launch_rollout_min_md(a, c->dist_mode, c->stream); });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(final_state, base + o_out, sw, hipMemcpyDeviceToHost, c->stream));
-  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_ss, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (vi_status) HIPCHK(c, hipMemcpyAsync(vi_status, base + o_vs, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  collect(c);
-  return GPRX_OK;
 }
 
 gprx_batch* gprx_gp_batch(gprx_gp* gp) { return gp ? gp->batch : nullptr; }

@@ -1,6 +1,8 @@
-// gprx_device.h -- lane-level pieces of the fp64 kernels: the MFMA wrapper, the block -> (slot, unit)
-// mapping, distance and exp arithmetic with its tables, lane and wave reductions, buffer loads and
-// stores, and the z-partial rows.
+// gprx_device.h -- lane-level pieces of the evaluation kernels: the MFMA wrapper, the block -> (slot,
+// unit) mapping, the exp arithmetic with its tables, the DPP / lane-swap row and wave reductions,
+// buffer loads and stores, and the z-partial rows.  (The distance forms sqd2 / wacc and the plain
+// readlane_d / wave_sum use no device global and live in gprx_internal.h, where gprx_projection.hip
+// finds them too.)
 //
 // gprx_kernels.hip is one translation unit cut along its banners.  It includes, in this order:
 //   gprx_device.h, gprx_cores.h, gprx_stamps.h   (before its first kernel)
@@ -65,28 +67,6 @@ __device__ __forceinline__ void pair_unit(int u, int R, int C, bool tri, int& r,
   }
   c = cc;
   r = cc + 2 * u;
-}
-
-// Squared distance along one input dimension.
-//  EXPANDED: Distances.jl 0.10.5 _pairwise!(r, SqEuclidean(), a, b) on the 1-row views that
-//            GaussianProcesses' StationaryARD KernelData builds: max(a^2 + b^2 - 2(ab), 0).
-//            (s - 2t with t = fl(ab) equals fma(-2, t, s): 2t is exact.)
-//  DIRECT  : (a - b)^2.
-// The file is compiled with -ffp-contract=off so everything else rounds exactly as written.
-// sqd2: the expanded form with the squares precomputed.
-__device__ __forceinline__ double sqd2(double a, double a2, double b, double b2) {
-  const double v = fma(-2.0, a * b, a2 + b2);
-  return v > 0.0 ? v : 0.0;
-}
-// r + d(a, b) w.  Expanded mode keeps the Distances.jl stack's rounding (d, then w d, then +; 6 fp64
-// ops per element and dimension).  Direct mode is distij's s += (a-b)^2 w with the accumulation
-// fused (3 ops): a rounding-level reordering, like the reference's own @simd sum.  (k_gram and
-// k_pred_cross go one step further in direct mode: coordinates pre-scaled by 1/ell, 2 ops.)
-template <int MODE>
-__device__ __forceinline__ double wacc(double r, double a, double a2, double b, double b2, double w) {
-  if (MODE == 0) return r + sqd2(a, a2, b, b2) * w;
-  const double t = a - b;
-  return __builtin_fma(t * t, w, r);
 }
 
 // sqrt(p) and 1/sqrt(p) for p > 0 (normal range) by v_rsq_f64 + Newton: two steps on r = p^-1/2,
@@ -166,18 +146,6 @@ __device__ __forceinline__ double exp_sf(double x, const ExpK& k, const double* 
   return x < -745.0 ? 0.0 : v;
 }
 
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 // v from another lane of the same 16-lane row by a DPP control (two 32-bit DPP moves, no LDS)
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {

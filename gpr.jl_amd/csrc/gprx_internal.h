@@ -1,5 +1,6 @@
-// Internal declarations shared by the HIP kernels (gprx_kernels.hip) and the C-ABI host code
-// (gprx_api.hip).  Not part of the public ABI.
+// Internal declarations shared by the HIP kernels (gprx_kernels.hip, gprx_lbfgs.hip,
+// gprx_projection.hip) and the C-ABI host code (gprx_api.hip), and the device helpers that more than
+// one of the kernel files uses.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -121,8 +122,8 @@ __host__ __device__ inline void blk_range(int nt, int i, int& lo, int& hi) {
   hi = o + n;
 }
 
-// Minimal-coordinate rollout (k_rollout): one GP of a rollout group, read from a batch slot after
-// its factorisation (X: [Npad][d], alpha: Npad, params: il2[d], sf2, ...).
+// Rollouts (k_rollout, k_rollout_max; gprx_projection.hip): one GP of a rollout group, read from a
+// batch slot after its factorisation (X: [Npad][d], alpha: Npad, params: il2[d], sf2, ...).
 struct RolloutGP {
   const double* X;
   const double* alpha;
@@ -184,9 +185,9 @@ struct RolloutMaxArgs {
   double* perr;         // T mean projection error per step
   int* status;          // T: 0 ok, 1 singular projection, 2 failed physics mean (MeanDynamics)
 };
-// MeanDynamics GPs (k_rollout_max_md, k_rollout_min_md): the variational-integrator step that gives
-// the prior mean at every step's state.  Kept apart from RolloutMaxArgs, so k_rollout_max's kernel
-// arguments are what they were.
+// MeanDynamics GPs (the RolloutMaxMdArgs / RolloutMinMdArgs instantiations of k_rollout_max and
+// k_rollout): the variational-integrator step that gives the prior mean at every step's state.  Kept
+// apart from the MeanZero structs, so those kernels' arguments are what they were.
 struct RolloutViArgs {
   double reg, eps, grav;
   int iters;
@@ -195,18 +196,14 @@ struct RolloutViArgs {
 struct RolloutMaxMdArgs : RolloutMaxArgs {
   RolloutViArgs vi;
 };
-// predictdynamicsmin with MeanDynamics GPs (k_rollout_min_md): RolloutArgs' rollout plus, per step,
-// the experiments' xtransform of the features into a CState and one variational-integrator step
-struct RolloutMinMdArgs {
+// predictdynamicsmin with MeanDynamics GPs: RolloutArgs' rollout plus, per step, the experiments'
+// xtransform of the features into a CState and one variational-integrator step.  A failed physics
+// mean leaves a NaN row in out.
+struct RolloutMinMdArgs : RolloutArgs {
   MechDev mech;
-  const RolloutGP* gps;  // ngroups x nc
-  const int* group;      // T
-  const double* start;   // T x 2nc
-  double* out;           // T x 2nc: (q_cur, qdot_last) per coordinate (NaN row: failed physics mean)
-  int* status;           // T: 0 ok, 2 failed physics mean
-  int T, nc, d, steps, mech_id;
-  int usesin, ang0, ang1;
-  double dt, len[2];     // link lengths (gprx/rollout.py LENGTHS)
+  int mech_id;
+  double len[2];        // link lengths (gprx/rollout.py LENGTHS)
+  int* status;          // T: 0 ok, 2 failed physics mean
   RolloutViArgs vi;
 };
 // One variational-integrator step (ConstrainedDynamics 0.7.4 newton!, restated in gprx/vi.py) for T
@@ -225,7 +222,46 @@ void launch_project(const ProjArgs& a, hipStream_t s);
 void launch_vi_step(const ViArgs& a, hipStream_t s);
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s);
+
+// ---- device helpers that use no device global, shared by gprx_kernels.hip and gprx_projection.hip
+// (gprx_device.h holds the ones that do and belongs to gprx_kernels.hip alone) --------------------
+// Squared distance along one input dimension.
+//  EXPANDED: Distances.jl 0.10.5 _pairwise!(r, SqEuclidean(), a, b) on the 1-row views that
+//            GaussianProcesses' StationaryARD KernelData builds: max(a^2 + b^2 - 2(ab), 0).
+//            (s - 2t with t = fl(ab) equals fma(-2, t, s): 2t is exact.)
+//  DIRECT  : (a - b)^2.
+// Every file is compiled with -ffp-contract=off so everything else rounds exactly as written.
+// sqd2: the expanded form with the squares precomputed.
+__device__ __forceinline__ double sqd2(double a, double a2, double b, double b2) {
+  const double v = fma(-2.0, a * b, a2 + b2);
+  return v > 0.0 ? v : 0.0;
+}
+// r + d(a, b) w.  Expanded mode keeps the Distances.jl stack's rounding (d, then w d, then +; 6 fp64
+// ops per element and dimension).  Direct mode is distij's s += (a-b)^2 w with the accumulation
+// fused (3 ops): a rounding-level reordering, like the reference's own @simd sum.  (k_gram and
+// k_pred_cross go one step further in direct mode: coordinates pre-scaled by 1/ell, 2 ops.)
+template <int MODE>
+__device__ __forceinline__ double wacc(double r, double a, double a2, double b, double b2, double w) {
+  if (MODE == 0) return r + sqd2(a, a2, b, b2) * w;
+  const double t = a - b;
+  return __builtin_fma(t * t, w, r);
+}
+
+// one lane's value on every lane (lane uniform); the sum over the wave's 64 lanes on every lane
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)b, lane);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // hyper-parameters -> kernel parameters for one slot, exactly as SEArd / GPE derive them:
 //   il2 = exp(-2 log ell), sf2 = exp(2 log sf), noise = exp(2 logNoise) + eps();
@@ -297,7 +333,6 @@ int lauum_plan(int nt, int d, int* nunits, int* nimg, int* out);
 void launch_finalize(const DevBatch& b, int want_grad, hipStream_t s);
 void launch_pred_cross(const DevBatch& b, hipStream_t s);
 void launch_pred_final(const DevBatch& b, hipStream_t s);
-void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s);
 // joint predictive covariance and samples (gprx_predcov.h).  VT: B x [Npad][Mpad] (K*^T's layout);
 // Sig: B x [M][M] compact; F: the factor, ld = M, slot stride fs doubles; Z / smp: [S][M] per slot
 // at strides zs (0 = shared) / ss; jit[B], st[B] as k_cov_chol writes them

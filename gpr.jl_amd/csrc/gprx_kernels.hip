@@ -12,6 +12,7 @@
 //           W = alpha alpha^T - K^-1 against dK/dtheta (K^-1 never written to HBM)   (lauum_grad)
 //   mll, dmll                                                                        (finalize)
 //   mu* = k*^T alpha,  var* = max(sf2 - |L^-1 k*|^2, 0)                             (pred_*)
+// The rollouts (k_rollout, k_rollout_max) and their physics are in gprx_projection.hip.
 //
 // Dense products: one wave computes a 64x32 block with v_mfma_f64_16x16x4_f64 (4x2 16x16
 // accumulators), operands streamed straight from L2 one 16-deep stage ahead (fp64 MFMA is 64
@@ -996,111 +997,6 @@ __global__ __launch_bounds__(NTHR) void k_pred_final(DevBatch db) {
 }
 
 
-// ============================================================================================
-// Rollout in minimal coordinates (examples/utils/predictdynamics.jl:30-102, predictdynamicsmin):
-// per trajectory, `steps` rounds of  obs = f(q_old, qdot_old);  qdot_cur_g = mu_g(obs) for each of
-// the nc GPs;  (q_old, qdot_old) = (q_cur, qdot_cur);  q_cur += qdot_cur dt.  One workgroup per
-// trajectory runs the whole rollout (the step chain is serial, so it is latency-bound; one launch
-// instead of steps x nc predict calls).  mu_g = sum_j sf2 exp(-r_j/2) alpha_j with r_j summed as
-// distij does (il2-weighted; k_pred_cross sums coordinates pre-scaled by sqrt(il2/2) instead),
-// so a rollout step reproduces gprx_batch_predict's mean up to rounding: the distance sums', the
-// exp's (libm's here, k_pred_cross's table exp_sf) and the order of the final sum.  The state updates use
-// explicit round-to-nearest mul/add (no fma contraction), as the reference's Julia arithmetic.
-// ============================================================================================
-__device__ __forceinline__ double pick3(const double (&e)[3], int i) {
-  return i == 0 ? e[0] : (i == 1 ? e[1] : (i == 2 ? e[2] : 0.0));
-}
-
-template <int MODE, int NT>
-__global__ __launch_bounds__(NT) void k_rollout(RolloutArgs a) {
-  constexpr int NW = NT / 64, U = NT >= 1024 ? 2 : 4;  // training points per thread in flight
-  __shared__ double red[2][NW][2];
-  const int t = blockIdx.x, tid = threadIdx.x, nc = a.nc, d = a.d;
-  const RolloutGP* gp = a.gps + (size_t)a.group[t] * nc;
-  double qo[2], vo[2], qc[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    qo[c] = c < nc ? a.start[(size_t)t * 2 * nc + 2 * c] : 0.0;
-    vo[c] = c < nc ? a.start[(size_t)t * 2 * nc + 2 * c + 1] : 0.0;
-    qc[c] = __dadd_rn(qo[c], __dmul_rn(a.dt, vo[c]));
-  }
-  const bool s0 = a.usesin && a.ang0, s1 = a.usesin && a.ang1;
-  const int w0 = s0 ? 3 : 2;
-  for (int step = 0; step < a.steps; ++step) {
-    double e0[3], e1[3];
-    e0[0] = s0 ? sin(qo[0]) : qo[0];
-    e0[1] = s0 ? cos(qo[0]) : vo[0];
-    e0[2] = s0 ? vo[0] : 0.0;
-    e1[0] = s1 ? sin(qo[1]) : qo[1];
-    e1[1] = s1 ? cos(qo[1]) : vo[1];
-    e1[2] = s1 ? vo[1] : 0.0;
-    double ov[6], ov2[6];
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      ov[p] = p < w0 ? pick3(e0, p) : pick3(e1, p - w0);
-      ov2[p] = ov[p] * ov[p];
-    }
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      if (g >= nc) break;
-      const RolloutGP G = gp[g];
-      double il2[6];
-#pragma unroll
-      for (int p = 0; p < 6; ++p) il2[p] = p < d ? G.params[p] : 0.0;
-      const double sf2 = G.params[d];
-      double s = 0.0;
-      // points j = tid + NT k in increasing k (the same order as a plain strided loop), U at a time
-      for (int j0 = tid; j0 < G.N; j0 += U * NT) {
-        double xv[U][6], al[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int j = j0 + u * NT;
-          const bool ok = j < G.N;
-          const double* x = G.X + (size_t)(ok ? j : 0) * d;
-#pragma unroll
-          for (int p = 0; p < 6; ++p) xv[u][p] = p < d ? x[p] : 0.0;
-          al[u] = ok ? G.alpha[j] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          double r = 0.0;
-#pragma unroll
-          for (int p = 0; p < 6; ++p)
-            if (p < d) r = wacc<MODE>(r, xv[u][p], xv[u][p] * xv[u][p], ov[p], ov2[p], il2[p]);
-          if (j0 + u * NT < G.N) s = fma(sf2 * exp(-r * 0.5), al[u], s);
-        }
-      }
-      acc[g] = wave_sum(s);
-    }
-    const int par = step & 1;
-    if ((tid & 63) == 0) {
-      red[par][tid >> 6][0] = acc[0];
-      red[par][tid >> 6][1] = acc[1];
-    }
-    __syncthreads();  // red[par] is rewritten two steps later, after this step's reads
-    double pred[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      double v = red[par][0][g];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) v += red[par][w][g];
-      pred[g] = v;
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      qo[c] = qc[c];
-      vo[c] = pred[c];
-      qc[c] = __dadd_rn(qc[c], __dmul_rn(pred[c], a.dt));
-    }
-  }
-  if (tid == 0)
-    for (int c = 0; c < nc; ++c) {
-      a.out[(size_t)t * 2 * nc + 2 * c] = qc[c];
-      a.out[(size_t)t * 2 * nc + 2 * c + 1] = vo[c];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -1189,13 +1085,6 @@ void launch_pred_cross(const DevBatch& b, hipStream_t s) {
 }
 void launch_pred_final(const DevBatch& b, hipStream_t s) {
   hipLaunchKernelGGL(k_pred_final, dim3(b.B), dim3(NTHR), 0, s, b);
-}
-void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s) {
-  // 256 threads per trajectory for every T (measured: 512 is 0.04 ms faster for 100 trajectories,
-  // 256 is 1.4x faster for 3200; a fixed size keeps each trajectory's sums independent of T)
-  if (a.T <= 0) return;
-  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout<0, 256>), dim3(a.T), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_rollout<1, 256>), dim3(a.T), dim3(256), 0, s, a);
 }
 
 }  // namespace gprx

@@ -18,6 +18,9 @@
 // workgroup per trajectory runs every step on the device -- the G GPs' mean predictions at the
 // current CState (the training points split over the workgroup), getvw, the projection (its LU
 // update over the whole workgroup), the projection error and updatestate!.
+//
+// predictdynamicsmin (:30-102), the rollout in minimal coordinates (k_rollout), is here too: with
+// MeanDynamics GPs each of its steps runs the variational-integrator solve below.
 #include "gprx_internal.h"
 #include <type_traits>
 
@@ -113,6 +116,11 @@ __device__ __forceinline__ double* pj_lds() {
 __host__ __device__ inline size_t pj_lds_bytes(int nb, int nd) {
   const size_t n = 6 * (size_t)nb + nd;
   return 2 * n * (n + 1) * sizeof(double);
+}
+// the variational-integrator step's dynamic LDS: its Newton matrix (n x (n + 1)) and Gpos (nd x 6 nb)
+__host__ __device__ inline size_t vi_lds_doubles(int nb, int nd) {
+  const size_t n = 6 * (size_t)nb + nd;
+  return n * (n + 1) + (size_t)nd * 6 * nb;
 }
 __device__ __forceinline__ Qd ldq(const double* q) { return Qd{q[0], q[1], q[2], q[3]}; }
 
@@ -248,17 +256,6 @@ __device__ void subjoint(PState& P, const SubJoint& J, int n6, int ldf, double d
   }
 }
 
-__device__ __forceinline__ double readlane_dbl(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // f(s) upper part: -su + s_v + G^T lambda (G read from F's lower-left block), lanes over columns
 __device__ __forceinline__ void residual_upper(PState& P, int n6, int nd, int ldf, int l) {
   if (l < n6) {
@@ -309,7 +306,7 @@ __device__ bool lu_solve(double* A, int n, int ldf, double& b) {
         A[k * ldf + j] = A[p * ldf + j];
         A[p * ldf + j] = t;
       }
-      const double bk = readlane_dbl(b, k), bp = readlane_dbl(b, p);
+      const double bk = readlane_d(b, k), bp = readlane_d(b, p);
       if (l == k) b = bp;
       if (l == p) b = bk;
     }
@@ -340,12 +337,12 @@ __device__ bool lu_solve(double* A, int n, int ldf, double& b) {
   if (singular) return true;
   // forward substitution (unit lower), then backward (upper), as dgetrs / dtrsm
   for (int k = 0; k < n; ++k) {
-    const double bk = readlane_dbl(b, k);
+    const double bk = readlane_d(b, k);
     if (bk != 0.0 && l > k && l < n) b = b - bk * A[l * ldf + k];
   }
   for (int k = n - 1; k >= 0; --k) {
     const double ukk = A[k * ldf + k];
-    double bk = readlane_dbl(b, k);
+    double bk = readlane_d(b, k);
     if (bk != 0.0) {
       bk = bk / ukk;
       if (l == k) b = bk;
@@ -409,7 +406,7 @@ __device__ void project(PState& P, const MechDev& M, double dt, double reg, doub
     if (w0) residual_upper(P, n6, nd, ldf, l);
     pj_sync<NW>();
     const double fv = l < n ? P.f[l] : 0.0, dv = l < n ? P.ds[l] : 0.0;
-    const double nf = sqrt(wsum(fv * fv)), nds = sqrt(wsum(dv * dv));
+    const double nf = sqrt(wave_sum(fv * fv)), nds = sqrt(wave_sum(dv * dv));
     if (tid == 0) P.it = it;
     pj_sync<NW>();
     if (nf < eps && nds < eps) break;
@@ -671,7 +668,7 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
     if (w0 && l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, grav, l);
     pj_sync<NW>();
     const double fv = l < n ? P.f[l] : 0.0, dv = l < n ? P.ds[l] : 0.0;
-    const double nf = sqrt(wsum(fv * fv)), nds = sqrt(wsum(dv * dv));
+    const double nf = sqrt(wave_sum(fv * fv)), nds = sqrt(wave_sum(dv * dv));
     if (nf < eps && nds < eps) {
       status = 0;
       break;
@@ -738,11 +735,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // __device__ body called by two kernels changed its register allocation).  The MeanDynamics form
 // drops the four-waves-per-SIMD hint: in the 128 registers that leaves, the solve spills to scratch.
 __host__ __device__ inline size_t md_mat_doubles(int nb, int nd) {
-  const size_t n = 6 * (size_t)nb + nd, pj = 2 * n * (n + 1), vi = n * (n + 1) + (size_t)nd * 6 * nb;
+  const size_t n = 6 * (size_t)nb + nd, pj = 2 * n * (n + 1), vi = vi_lds_doubles(nb, nd);
   return pj > vi ? pj : vi;
 }
 template <class Args>
-constexpr bool is_md = std::is_same_v<Args, RolloutMaxMdArgs>;
+constexpr bool is_md = std::is_same_v<Args, RolloutMaxMdArgs> || std::is_same_v<Args, RolloutMinMdArgs>;
 template <int MODE, class Args>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(is_md<Args> ? 1 : 4, is_md<Args> ? 2 : 4)))
 void k_rollout_max(Args a) {
@@ -796,7 +793,7 @@ void k_rollout_max(Args a) {
         }
         sacc = fma(sf2 * exp(-r * 0.5), Gp.alpha[j], sacc);
       }
-      sacc = wsum(sacc);
+      sacc = wave_sum(sacc);
       if (l == 0) red[w][g] = sacc;
     }
     __syncthreads();
@@ -829,7 +826,7 @@ void k_rollout_max(Args a) {
     if (w == 0) {
       // projection error |(v, w)_const - (v, w)_pred| (predictdynamics.jl:16), then updatestate!
       const double dv = l < n6 ? P.s[l] - P.su[l] : 0.0;
-      const double e = sqrt(wsum(dv * dv));
+      const double e = sqrt(wave_sum(dv * dv));
       if (l == 0) perr_s += e;
       update_state(P, nb, a.dt, l);
       __builtin_amdgcn_wave_barrier();
@@ -849,7 +846,7 @@ void k_rollout_max(Args a) {
     }
   }
 }
-// ---- predictdynamicsmin with MeanDynamics GPs: one workgroup per trajectory ----------------------
+// ---- the minimal coordinates' CState (predictdynamicsmin with MeanDynamics GPs) ------------------
 // The experiments' xtransform (examples/minimal_coordinates/*noise.jl, restated in
 // gprx/mdynamics.py xtransform, whose operation order this keeps) for body b: the CState of the
 // mechanism at the minimal coordinates (a0, a1) with rates (r0, r1), the linear velocities by the
@@ -931,21 +928,34 @@ static __device__ __forceinline__ void min_cstate_body(int mech, int b, double a
   c[12] = 0.0;
 }
 
-// Per step (examples/utils/predictdynamics.jl:30-102 with src/mDynamics.jl:41-55): the features of
-// (q_old, qdot_old) as k_rollout builds them, the nc GP means there (k_rollout_max's loop, both
-// distance modes), the CState of the features (min_cstate_body; the angle is atan2(sin, cos) when
-// usesin), set_states and vi_newton on the whole workgroup, the rates read from the solution
-// (gprx/mdynamics.py MIN_IDX / mean_min), rate = GP mean + physics rate, and k_rollout's explicit
-// round-to-nearest update.  Every thread keeps the coordinates (the same values).
-template <int MODE>
-__global__ __launch_bounds__(256) void k_rollout_min_md(RolloutMinMdArgs a) {
-  constexpr int NT = 256, NW = NT / 64;
-  __shared__ PState Q;
-  __shared__ double mom1[PJ_MAXB][3];
-  __shared__ double cs[13 * PJ_MAXB];
-  __shared__ double red[NW][2];
-  const int t = blockIdx.x, tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-  const int nc = a.nc, d = a.d, nb = a.mech.nb;
+// ---- predictdynamicsmin (examples/utils/predictdynamics.jl:30-102): one workgroup per trajectory ---
+// `steps` rounds of  obs = f(q_old, qdot_old);  qdot_cur_g = mu_g(obs) for each of the nc GPs;
+// (q_old, qdot_old) = (q_cur, qdot_cur);  q_cur += qdot_cur dt.  The step chain is serial, so the
+// rollout is latency-bound: one launch instead of steps x nc predict calls.  mu_g = sum_j sf2
+// exp(-r_j/2) alpha_j with r_j summed as distij does (il2-weighted; k_pred_cross sums coordinates
+// pre-scaled by sqrt(il2/2) instead), so a rollout step reproduces gprx_batch_predict's mean up to
+// rounding: the distance sums', the exp's (libm's here, k_pred_cross's table exp_sf) and the order of
+// the final sum.  The state updates use explicit round-to-nearest mul/add (no fma contraction), as the
+// reference's Julia arithmetic.  Every thread keeps the coordinates (the same values).
+// One template over the argument type, as k_rollout_max: with RolloutArgs (MeanZero) the instructions
+// are those of the kernel before the MeanDynamics form existed.  With RolloutMinMdArgs
+// (src/mDynamics.jl:41-55) each step adds the physics mean: the CState of the features
+// (min_cstate_body; the angle is atan2(sin, cos) when usesin), set_states and vi_newton on the whole
+// workgroup, and the rates read from the solution (gprx/mdynamics.py MIN_IDX / mean_min) added to the
+// GP means.  A failed physics step (status 2: the reference throws) stops the trajectory.
+__device__ __forceinline__ double pick3(const double (&e)[3], int i) {
+  return i == 0 ? e[0] : (i == 1 ? e[1] : (i == 2 ? e[2] : 0.0));
+}
+
+template <int MODE, class Args>
+__global__ __launch_bounds__(256) void k_rollout(Args a) {
+  constexpr bool MD = is_md<Args>;
+  constexpr int NT = 256, NW = NT / 64, U = 4;  // U training points per thread in flight
+  __shared__ double red[2][NW][2];
+  [[maybe_unused]] __shared__ PState Q;  // the physics mean's state, (sq1 I - [w1 x]) J w1 and CState
+  [[maybe_unused]] __shared__ double mom1[PJ_MAXB][3];
+  [[maybe_unused]] __shared__ double cs[13 * PJ_MAXB];
+  const int t = blockIdx.x, tid = threadIdx.x, nc = a.nc, d = a.d;
   const RolloutGP* gp = a.gps + (size_t)a.group[t] * nc;
   double qo[2], vo[2], qc[2];
 #pragma unroll
@@ -956,89 +966,118 @@ __global__ __launch_bounds__(256) void k_rollout_min_md(RolloutMinMdArgs a) {
   }
   const bool s0 = a.usesin && a.ang0, s1 = a.usesin && a.ang1;
   const int w0 = s0 ? 3 : 2;
-  int vis = 0;
+  [[maybe_unused]] int vis = 0;
   bool failed = false;
   for (int step = 0; step < a.steps; ++step) {
-    const double e0[3] = {s0 ? sin(qo[0]) : qo[0], s0 ? cos(qo[0]) : vo[0], s0 ? vo[0] : 0.0};
-    const double e1[3] = {s1 ? sin(qo[1]) : qo[1], s1 ? cos(qo[1]) : vo[1], s1 ? vo[1] : 0.0};
-    double ov[ROLLOUT_DMAX];
+    double e0[3], e1[3];
+    e0[0] = s0 ? sin(qo[0]) : qo[0];
+    e0[1] = s0 ? cos(qo[0]) : vo[0];
+    e0[2] = s0 ? vo[0] : 0.0;
+    e1[0] = s1 ? sin(qo[1]) : qo[1];
+    e1[1] = s1 ? cos(qo[1]) : vo[1];
+    e1[2] = s1 ? vo[1] : 0.0;
+    double ov[ROLLOUT_DMAX], ov2[ROLLOUT_DMAX];
 #pragma unroll
     for (int p = 0; p < ROLLOUT_DMAX; ++p) {
-      const int q = p - w0;
-      ov[p] = p < w0 ? (p == 0 ? e0[0] : (p == 1 ? e0[1] : e0[2])) : (q == 0 ? e1[0] : (q == 1 ? e1[1] : (q == 2 ? e1[2] : 0.0)));
+      ov[p] = p < w0 ? pick3(e0, p) : pick3(e1, p - w0);
+      ov2[p] = ov[p] * ov[p];
     }
     // ---- mu_g = sum_j sf2 exp(-r_j / 2) alpha_j at the features
-    for (int g = 0; g < nc; ++g) {
-      const RolloutGP Gp = gp[g];
-      const double sf2 = Gp.params[d];
-      double sacc = 0.0;
-      for (int j = tid; j < Gp.N; j += NT) {
-        const double* x = Gp.X + (size_t)j * d;
-        double r = 0.0;
+    double acc[2] = {0.0, 0.0};
 #pragma unroll
-        for (int p = 0; p < ROLLOUT_DMAX; ++p) {
-          if (p < d) {
-            const double o = ov[p];
-            if (MODE == 0) {
-              const double v = fma(-2.0, x[p] * o, x[p] * x[p] + o * o);
-              r = r + (v > 0.0 ? v : 0.0) * Gp.params[p];
-            } else {
-              const double df = x[p] - o;
-              r = __builtin_fma(df * df, Gp.params[p], r);
-            }
-          }
+    for (int g = 0; g < 2; ++g) {
+      if (g >= nc) break;
+      const RolloutGP G = gp[g];
+      double il2[ROLLOUT_DMAX];
+#pragma unroll
+      for (int p = 0; p < ROLLOUT_DMAX; ++p) il2[p] = p < d ? G.params[p] : 0.0;
+      const double sf2 = G.params[d];
+      double s = 0.0;
+      // points j = tid + NT k in increasing k (the same order as a plain strided loop), U at a time
+      for (int j0 = tid; j0 < G.N; j0 += U * NT) {
+        double xv[U][ROLLOUT_DMAX], al[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int j = j0 + u * NT;
+          const bool ok = j < G.N;
+          const double* x = G.X + (size_t)(ok ? j : 0) * d;
+#pragma unroll
+          for (int p = 0; p < ROLLOUT_DMAX; ++p) xv[u][p] = p < d ? x[p] : 0.0;
+          al[u] = ok ? G.alpha[j] : 0.0;
         }
-        sacc = fma(sf2 * exp(-r * 0.5), Gp.alpha[j], sacc);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          double r = 0.0;
+#pragma unroll
+          for (int p = 0; p < ROLLOUT_DMAX; ++p)
+            if (p < d) r = wacc<MODE>(r, xv[u][p], xv[u][p] * xv[u][p], ov[p], ov2[p], il2[p]);
+          if (j0 + u * NT < G.N) s = fma(sf2 * exp(-r * 0.5), al[u], s);
+        }
       }
-      sacc = wsum(sacc);
-      if (l == 0) red[w][g] = sacc;
+      acc[g] = wave_sum(s);
     }
-    // ---- the physics mean: CState of the features, one variational-integrator step
-    const double a0 = s0 ? atan2(e0[0], e0[1]) : e0[0], r0 = s0 ? e0[2] : e0[1];
-    const double a1 = s1 ? atan2(e1[0], e1[1]) : e1[0], r1 = s1 ? e1[2] : e1[1];
-    if (w == 0 && l < nb) min_cstate_body(a.mech_id, l, a0, r0, a1, r1, a.len[0], a.len[1], cs + 13 * l);
-    __syncthreads();
-    if (w == 0) set_states(Q, cs, nb, a.dt, l);
-    __syncthreads();
-    int vit;
-    const int vs = vi_newton<NW>(Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
-    vis |= vs;
-    if (vs == 2) {  // the same on every wave: the reference throws, the trajectory stops
-      failed = true;
-      break;
+    const int par = step & 1;
+    if ((tid & 63) == 0) {
+      red[par][tid >> 6][0] = acc[0];
+      red[par][tid >> 6][1] = acc[1];
     }
-    // the solution's rates (0-based CState positions 13 b + k, k >= 7, at Q.s[6 b + k - 7]):
-    // P1 [11]; P2 (w1, w2 - w1) of bodies 1 and 2; CP [9, 24]; FB [11, 37] (1-based)
-    double phys[2];
-    if (a.mech_id == 2) {
-      phys[0] = Q.s[3];
-      phys[1] = Q.s[9] - Q.s[3];
-    } else if (a.mech_id == 3) {
-      phys[0] = Q.s[1];
-      phys[1] = Q.s[9];
-    } else {
-      phys[0] = Q.s[3];
-      phys[1] = a.mech_id == 4 ? Q.s[15] : 0.0;
+    [[maybe_unused]] double phys[2];
+    if constexpr (MD) {  // the physics mean: CState of the features, one variational-integrator step
+      const int nb = a.mech.nb;
+      const double a0 = s0 ? atan2(e0[0], e0[1]) : e0[0], r0 = s0 ? e0[2] : e0[1];
+      const double a1 = s1 ? atan2(e1[0], e1[1]) : e1[0], r1 = s1 ? e1[2] : e1[1];
+      if (tid < nb) min_cstate_body(a.mech_id, tid, a0, r0, a1, r1, a.len[0], a.len[1], cs + 13 * tid);
+      __syncthreads();
+      if (tid < 64) set_states(Q, cs, nb, a.dt, tid);
+      __syncthreads();
+      int vit;
+      const int vs = vi_newton<NW>(Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
+      vis |= vs;
+      if (vs == 2) {  // the same on every wave
+        failed = true;
+        break;
+      }
+      // the solution's rates (0-based CState positions 13 b + k, k >= 7, at Q.s[6 b + k - 7]):
+      // P1 [11]; P2 (w1, w2 - w1) of bodies 1 and 2; CP [9, 24]; FB [11, 37] (1-based)
+      if (a.mech_id == 2) {
+        phys[0] = Q.s[3];
+        phys[1] = Q.s[9] - Q.s[3];
+      } else if (a.mech_id == 3) {
+        phys[0] = Q.s[1];
+        phys[1] = Q.s[9];
+      } else {
+        phys[0] = Q.s[3];
+        phys[1] = a.mech_id == 4 ? Q.s[15] : 0.0;
+      }
+    }
+    // red[par] is rewritten two steps later, after this step's reads; Q and mom1 by the next step, whose
+    // writes follow this barrier and this step's reads of them precede it
+    __syncthreads();
+    double pred[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      double v = red[par][0][g];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v += red[par][w][g];
+      if constexpr (MD) v += phys[g];  // (a coordinate past nc has mean and rate 0 and is not written)
+      pred[g] = v;
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      double v = red[0][c];
-#pragma unroll
-      for (int q = 1; q < NW; ++q) v += red[q][c];
-      const double rate = c < nc ? v + phys[c] : 0.0;
       qo[c] = qc[c];
-      vo[c] = rate;
-      qc[c] = __dadd_rn(qc[c], __dmul_rn(rate, a.dt));
+      vo[c] = pred[c];
+      qc[c] = __dadd_rn(qc[c], __dmul_rn(pred[c], a.dt));
     }
-    __syncthreads();  // red, cs and Q are rewritten by the next step
   }
   if (tid == 0) {
     for (int c = 0; c < nc; ++c) {
       a.out[(size_t)t * 2 * nc + 2 * c] = failed ? NAN : qc[c];
       a.out[(size_t)t * 2 * nc + 2 * c + 1] = failed ? NAN : vo[c];
     }
-    a.status[t] = failed ? 2 : 0;
-    if (a.vi.status) a.vi.status[t] = vis;
+    if constexpr (MD) {
+      a.status[t] = failed ? 2 : 0;
+      if (a.vi.status) a.vi.status[t] = vis;
+    }
   }
 }
 
@@ -1046,10 +1085,7 @@ void launch_project(const ProjArgs& a, hipStream_t s) {
   if (a.T > 0) hipLaunchKernelGGL(k_project, dim3(a.T), dim3(64), pj_lds_bytes(a.mech.nb, a.mech.nd), s, a);
 }
 void launch_vi_step(const ViArgs& a, hipStream_t s) {
-  if (a.T <= 0) return;
-  const size_t n = 6 * (size_t)a.mech.nb + a.mech.nd;
-  const size_t lds = (n * (n + 1) + (size_t)a.mech.nd * 6 * a.mech.nb) * sizeof(double);
-  hipLaunchKernelGGL(k_vi_step, dim3(a.T), dim3(64), lds, s, a);
+  if (a.T > 0) hipLaunchKernelGGL(k_vi_step, dim3(a.T), dim3(64), vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s, a);
 }
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s) {
   if (a.T <= 0) return;
@@ -1064,12 +1100,17 @@ void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t
   if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
   else hipLaunchKernelGGL((k_rollout_max<1, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
 }
-void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s) {
+// 256 threads per trajectory for every T (measured: 512 is 0.04 ms faster for 100 trajectories, 256 is
+// 1.4x faster for 3200; a fixed size keeps each trajectory's sums independent of T)
+template <class Args>
+static void launch_rollout_min(const Args& a, int dist_mode, size_t lds, hipStream_t s) {
   if (a.T <= 0) return;
-  const size_t n = 6 * (size_t)a.mech.nb + a.mech.nd;
-  const size_t lds = (n * (n + 1) + (size_t)a.mech.nd * 6 * a.mech.nb) * sizeof(double);  // launch_vi_step's
-  if (dist_mode == 0) hipLaunchKernelGGL(k_rollout_min_md<0>, dim3(a.T), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(k_rollout_min_md<1>, dim3(a.T), dim3(256), lds, s, a);
+  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout<0, Args>), dim3(a.T), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((k_rollout<1, Args>), dim3(a.T), dim3(256), lds, s, a);
+}
+void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s) { launch_rollout_min(a, dist_mode, 0, s); }
+void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s) {
+  launch_rollout_min(a, dist_mode, vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s);
 }
 
 }  // namespace gprx

@@ -16,7 +16,7 @@ tests/test_vi_device.py).  Every function takes `physics` (a callable (mech, sta
 iterations, status)) to run the same logic on another implementation, e.g. physics=vi.vi_step.
 rollout_max / rollout_min are that stepwise path (three blocking device calls per step);
 rollout_max_device / rollout_min_device run every step of every trajectory in one launch
-(k_rollout_max's MeanDynamics form, k_rollout_min_md).
+(the MeanDynamics instantiations of k_rollout_max and k_rollout).
 
 Maximal coordinates (e.g. examples/maximal_coordinates/P2noise.jl:28-33): the CState input,
 getμ(vωindices) of the solution CState.  Minimal coordinates (e.g. minimal_coordinates/

@@ -15,8 +15,6 @@ pins it).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
@@ -95,7 +93,13 @@ def predictdynamics(mech: str, groups, start, steps: int, vw_indices, regularize
     slot) pairs or MeanZero GPEs -- factorised at their hyperparameters; start (T, 13 nb) CStates;
     vw_indices: the experiment's 1-based vwindices (output g's CState position).  Returns (final
     CStates (T, 13 nb), mean projection error per step (T,), status (T,))."""
-    from .rollout import _slot_ref
+    return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=False)[:3]
+
+
+def _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md, vi_regularizer=None):
+    """predictdynamics (md False: MeanZero GPs) and predictdynamics_md: (final CStates, projection
+    error, status, vi_status), the last None for MeanZero GPs."""
+    from .rollout import _device_args, _slot_ref, _slot_ref_md
 
     if mech not in MECH:
         raise ValueError(f"Experiment {mech} not supported!")
@@ -105,23 +109,24 @@ def predictdynamics(mech: str, groups, start, steps: int, vw_indices, regularize
     if S.shape != (T, 13 * nb):
         raise ValueError(f"start must be (T, {13 * nb})")
     G = len(vw_indices)
-    refs = []
-    for grp in groups:
-        if len(grp) != G:
-            raise ValueError(f"each group needs {G} GPs (one per vw index)")
-        refs += [_slot_ref(g) for g in grp]
-    tg = np.zeros(T, dtype=np.int32) if traj_group is None else np.ascontiguousarray(traj_group, dtype=np.int32)
-    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
-    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
+    ref = (lambda g, k: _slot_ref_md(g, mech, "max", k)) if md else (lambda g, k: _slot_ref(g))
+    batches, slots, tg, ctx = _device_args(groups, G, f"each group needs {G} GPs (one per vw index)", T, traj_group, ref, ctx)
     vwi = np.ascontiguousarray(vw_indices, dtype=np.int32)
     reg = REGULARIZER[mech] if regularizer is None else float(regularizer)
-    ctx = ctx or refs[0][0].ctx
     out = np.empty((T, 13 * nb))
     pe = np.empty(T)
     st = np.empty(T, dtype=np.int32)
-    L.check(L.lib.gprx_rollout_max(ctx.h, MECH[mech], float(dt), int(steps), reg, len(groups), batches, L.iptr(slots), G,
-                                   L.iptr(vwi), T, L.iptr(tg), L.dptr(S), L.dptr(out), L.dptr(pe), L.iptr(st)), ctx.h)
-    return out, pe, st
+    head = (ctx.h, MECH[mech], float(dt), int(steps), reg)
+    tail = (len(groups), batches, L.iptr(slots), G, L.iptr(vwi), T, L.iptr(tg), L.dptr(S), L.dptr(out), L.dptr(pe), L.iptr(st))
+    if not md:
+        L.check(L.lib.gprx_rollout_max(*head, *tail), ctx.h)
+        return out, pe, st, None
+    from . import vi
+
+    vreg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
+    vst = np.empty(T, dtype=np.int32)
+    L.check(L.lib.gprx_rollout_max_md(*head, vreg, *tail, L.iptr(vst)), ctx.h)
+    return out, pe, st, vst
 
 
 def predictdynamics_md(mech: str, groups, start, steps: int, vw_indices, regularizer: float | None = None,
@@ -133,39 +138,8 @@ def predictdynamics_md(mech: str, groups, start, steps: int, vw_indices, regular
     that carry MeanDynamics(mech, g + 1, "max").  Returns (final CStates (T, 13 nb), mean projection
     error per step (T,), status (T,): 1 = singular projection, 2 = a failed physics step, the row is
     NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
-    from . import vi
-    from .rollout import _slot_ref_md
-
-    if mech not in MECH:
-        raise ValueError(f"Experiment {mech} not supported!")
-    nb = NBODIES[mech]
-    S = np.ascontiguousarray(np.atleast_2d(start), dtype=np.float64)
-    T = S.shape[0]
-    if S.shape != (T, 13 * nb):
-        raise ValueError(f"start must be (T, {13 * nb})")
-    G = len(vw_indices)
-    refs = []
-    for grp in groups:
-        if len(grp) != G:
-            raise ValueError(f"each group needs {G} GPs (one per vw index)")
-        refs += [_slot_ref_md(g, mech, "max", k) for k, g in enumerate(grp)]
-    tg = np.zeros(T, dtype=np.int32) if traj_group is None else np.ascontiguousarray(traj_group, dtype=np.int32)
-    if tg.shape != (T,):
-        raise ValueError("traj_group must have one entry per trajectory")
-    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
-    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
-    vwi = np.ascontiguousarray(vw_indices, dtype=np.int32)
-    reg = REGULARIZER[mech] if regularizer is None else float(regularizer)
-    vreg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
-    ctx = ctx or refs[0][0].ctx
-    out = np.empty((T, 13 * nb))
-    pe = np.empty(T)
-    st = np.empty(T, dtype=np.int32)
-    vst = np.empty(T, dtype=np.int32)
-    L.check(L.lib.gprx_rollout_max_md(ctx.h, MECH[mech], float(dt), int(steps), reg, vreg, len(groups), batches, L.iptr(slots),
-                                      G, L.iptr(vwi), T, L.iptr(tg), L.dptr(S), L.dptr(out), L.dptr(pe), L.iptr(st),
-                                      L.iptr(vst)), ctx.h)
-    return out, pe, st, vst
+    return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=True,
+                            vi_regularizer=vi_regularizer)
 
 
 def _default_ctx():

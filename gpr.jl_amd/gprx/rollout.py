@@ -45,6 +45,29 @@ def rollout_min(mech: str, groups, start, steps: int, usesin: bool = False, dt: 
     GPE or a (GPBatch, slot) pair -- for coordinates 1..nc.  start: (T, 2nc).  traj_group: (T,)
     group index per trajectory (default: all group 0).  Returns (T, 2nc) = (q_cur, qdot_last) per
     coordinate after `steps` steps."""
+    return _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md=False)[0]
+
+
+def _device_args(groups, n: int, what: str, T: int, traj_group, ref, ctx):
+    """What the device rollouts share: the GP references of `groups` (n per group, GP k of a group
+    resolved by ref(g, k)) as the C calls take them, and the (T,) group index per trajectory.
+    Returns (batches, slots, traj_group, ctx); the arrays must outlive the call."""
+    tg = np.zeros(T, dtype=np.int32) if traj_group is None else np.ascontiguousarray(traj_group, dtype=np.int32)
+    if tg.shape != (T,):
+        raise ValueError("traj_group must have one entry per trajectory")
+    refs = []
+    for grp in groups:
+        if len(grp) != n:
+            raise ValueError(what)
+        refs += [ref(g, k) for k, g in enumerate(grp)]
+    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
+    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
+    return batches, slots, tg, ctx or refs[0][0].ctx
+
+
+def _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md, vi_regularizer=None):
+    """rollout_min (md False: MeanZero GPs) and rollout_min_md: (final, status, vi_status), the last
+    two None for MeanZero GPs."""
     if mech not in MECH:
         raise ValueError(f"Experiment {mech} not supported!")  # predictdynamics.jl:35
     nc = NCOORD[mech]
@@ -54,27 +77,22 @@ def rollout_min(mech: str, groups, start, steps: int, usesin: bool = False, dt: 
     T = start.shape[0]
     if start.shape != (T, 2 * nc):
         raise ValueError(f"start must be (T, {2 * nc})")
-    if traj_group is None:
-        traj_group = np.zeros(T, dtype=np.int32)
-    traj_group = np.ascontiguousarray(traj_group, dtype=np.int32)
-    if traj_group.shape != (T,):
-        raise ValueError("traj_group must have one entry per trajectory")
-    refs = []
-    for grp in groups:
-        if len(grp) != nc:
-            raise ValueError(f"{mech} rollouts use {nc} GP(s) per group")
-        for g in grp:
-            refs.append(_slot_ref(g))
-    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
-    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
-    ctx = ctx or refs[0][0].ctx
+    variant = "min_sin" if usesin else "min"
+    ref = (lambda g, k: _slot_ref_md(g, mech, variant, k)) if md else (lambda g, k: _slot_ref(g))
+    batches, slots, tg, ctx = _device_args(groups, nc, f"{mech} rollouts use {nc} GP(s) per group", T, traj_group, ref, ctx)
     out = np.empty((T, 2 * nc), dtype=np.float64)
-    L.check(
-        L.lib.gprx_rollout_min(ctx.h, MECH[mech], 1 if usesin else 0, float(dt), int(steps), len(groups), batches,
-                               L.iptr(slots), T, L.iptr(traj_group), L.dptr(start), L.dptr(out)),
-        ctx.h,
-    )
-    return out
+    head = (ctx.h, MECH[mech], 1 if usesin else 0, float(dt), int(steps))
+    tail = (len(groups), batches, L.iptr(slots), T, L.iptr(tg), L.dptr(start), L.dptr(out))
+    if not md:
+        L.check(L.lib.gprx_rollout_min(*head, *tail), ctx.h)
+        return out, None, None
+    from . import vi
+
+    reg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
+    st = np.empty(T, dtype=np.int32)
+    vst = np.empty(T, dtype=np.int32)
+    L.check(L.lib.gprx_rollout_min_md(*head, reg, *tail, L.iptr(st), L.iptr(vst)), ctx.h)
+    return out, st, vst
 
 
 def _slot_ref(g):
@@ -114,40 +132,7 @@ def rollout_min_md(mech: str, groups, start, steps: int, usesin: bool = False, d
     rollout_min's, of (GPBatch, slot) pairs factorised on y - μ(X) or GPEs that carry
     MeanDynamics(mech, g + 1, "min" / "min_sin").  Returns (final (T, 2nc), status (T,): 2 = a failed
     physics step, the row is NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
-    from . import vi
-
-    if mech not in MECH:
-        raise ValueError(f"Experiment {mech} not supported!")
-    nc = NCOORD[mech]
-    start = np.ascontiguousarray(start, dtype=np.float64)
-    if start.ndim == 1:
-        start = start[None, :]
-    T = start.shape[0]
-    if start.shape != (T, 2 * nc):
-        raise ValueError(f"start must be (T, {2 * nc})")
-    if traj_group is None:
-        traj_group = np.zeros(T, dtype=np.int32)
-    traj_group = np.ascontiguousarray(traj_group, dtype=np.int32)
-    if traj_group.shape != (T,):
-        raise ValueError("traj_group must have one entry per trajectory")
-    refs = []
-    for grp in groups:
-        if len(grp) != nc:
-            raise ValueError(f"{mech} rollouts use {nc} GP(s) per group")
-        refs += [_slot_ref_md(g, mech, "min_sin" if usesin else "min", k) for k, g in enumerate(grp)]
-    batches = (C.c_void_p * len(refs))(*[b.h.value for b, _ in refs])
-    slots = np.ascontiguousarray([s for _, s in refs], dtype=np.int32)
-    reg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
-    ctx = ctx or refs[0][0].ctx
-    out = np.empty((T, 2 * nc), dtype=np.float64)
-    st = np.empty(T, dtype=np.int32)
-    vst = np.empty(T, dtype=np.int32)
-    L.check(
-        L.lib.gprx_rollout_min_md(ctx.h, MECH[mech], 1 if usesin else 0, float(dt), int(steps), reg, len(groups), batches,
-                                  L.iptr(slots), T, L.iptr(traj_group), L.dptr(start), L.dptr(out), L.iptr(st), L.iptr(vst)),
-        ctx.h,
-    )
-    return out, st, vst
+    return _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md=True, vi_regularizer=vi_regularizer)
 
 
 def _rotx_q(th):
