@@ -54,6 +54,11 @@ struct gprx_ctx {
   // replay each batch's launch sequence as a hipGraph (GPRX_OPT_GRAPHS).  Off by default: measured
   // equal to direct launches at B=1..192 (the launches are queued far ahead of the GPU).
   bool use_graphs = false;
+  // GPRX_OPT_ACTIVE_DIMS: gprx_batch_set_train looks for the input dimensions that are constant and
+  // direct-mode evaluations skip them (DevBatch::da).  last_da: the count the latest evaluation or
+  // gprx_batch_set_train of this context ran with (gprx_ctx_kernel_stats "active_dims").
+  bool active_dims = true;
+  int last_da = 0;
   std::set<gprx_batch*> batches;      // live batches (destroyed with the context)
   void* rbuf = nullptr;               // rollout argument buffer (device), grown on demand
   size_t rcap = 0;
@@ -84,6 +89,10 @@ struct gprx_batch {
   bool factored = false;
   bool have_train = false;
   bool have_test = false;
+  // the non-constant dimensions gprx_batch_set_train found (every dimension with the option off);
+  // as a bit per dimension; db.amask holds what Xc was written for, which is this set in direct
+  // mode (sync_active)
+  unsigned long long found_mask = 0;
   // captured evaluation graphs, one per (want_grad, want_pred); valid while the key matches
   hipGraphExec_t gexec[4] = {};
   DevBatch gkey[4];
@@ -172,6 +181,14 @@ bool cov_addressable(int M_max) { return test_capacity(M_max) * test_capacity(M_
 
 // The dimensions every buffer size follows from (sizes_addressable first): the training side once,
 // at creation; the test side whenever the capacity for test points changes.
+// The active dimensions of the evaluation kernels and what follows from their count.
+unsigned long long all_dims(int d) { return d >= 64 ? ~0ull : (1ull << d) - 1ull; }
+void set_active(DevBatch& db, unsigned long long mask) {
+  db.amask = mask;
+  db.da = __builtin_popcountll(mask);
+  db.xs = db.da | 1;
+  db.gps = db.da + 2;
+}
 void set_train_dims(DevBatch& db, int B, int d, int N) {
   db.B = B;
   db.d = d;
@@ -181,10 +198,11 @@ void set_train_dims(DevBatch& db, int B, int d, int N) {
   db.ntl = db.nt * (db.nt + 1) / 2;
   db.ld = db.Npad;
   db.mat = (size_t)db.Npad * db.Npad;
-  db.xs = d | 1;
   db.pst = d + 4;
-  db.gps = d + 2;
+  // the gradient's units are planned for all d dimensions, whatever the active set: the partition
+  // fixes the order in which the partial sums are added, so it must not follow da
   db.nlj = gprx::lauum_plan(db.nt, d, &db.ngu, &db.nimg, nullptr);
+  set_active(db, all_dims(d));
 }
 void set_test_dims(DevBatch& db, int M_max) {
   db.M = 0;
@@ -216,11 +234,12 @@ using BufList = std::vector<Buf>;
 BufList train_bufs(gprx_batch& b) {
   DevBatch& db = b.db;
   const size_t B = db.B, Np = db.Npad, d = db.d;
-  return {dev(db.X, B * Np * d, true), dev(db.Xc, B * Np * db.xs), dev(db.Y, B * Np, true), dev(db.K, B * db.mat),
+  // Xc and grad_part are sized for all d dimensions (an active set uses their front)
+  return {dev(db.X, B * Np * d, true), dev(db.Xc, B * Np * (d | 1)), dev(db.Y, B * Np, true), dev(db.K, B * db.mat),
           dev(db.S, B * db.mat, true), dev(db.Lw, B * db.mat, true), dev(db.Linv, B * db.mat, true),
           dev(db.Mt, B * db.mat, true), dev(db.z, B * Np), dev(db.zp, B * 2 * db.nt * Np), dev(db.alpha, B * Np),
           dev(db.params, B * db.pst), dev(db.theta, B * (d + 2)), dev(db.logdet_part, B * db.nt),
-          dev(db.grad_part, B * db.ngu * db.gps), dev(db.out, B * (d + 3)), dev(db.status, 2 * B) /* status, info */,
+          dev(db.grad_part, B * db.ngu * (d + 2)), dev(db.out, B * (d + 3)), dev(db.status, 2 * B) /* status, info */,
           dev(db.lauum_order, 2 * gprx::LU * (size_t)std::max(db.nlj, 0)), dev(b.opt_active, B),
           pin(b.h_params, B * db.pst), pin(b.h_out, B * (d + 3)), pin(b.h_status, 2 * B)};
 }
@@ -457,6 +476,26 @@ int run_eval(gprx_batch* b, bool want_grad, bool want_pred, bool factor) {
   return GPRX_OK;
 }
 
+// Before an evaluation: Xc and the active list follow the context's distance mode.  Direct mode
+// takes the list gprx_batch_set_train found; expanded mode keeps every dimension (a^2 + b^2 - 2ab of
+// a constant is no exact zero).  A change re-centres Xc on the stream and drops the captured graphs,
+// which hold DevBatch by value.
+int sync_active(gprx_batch* b) {
+  gprx_ctx* c = b->ctx;
+  DevBatch& db = b->db;
+  const unsigned long long mask = c->dist_mode == GPRX_DIST_DIRECT ? b->found_mask : all_dims(db.d);
+  c->last_da = __builtin_popcountll(mask);
+  if (mask == db.amask) return GPRX_OK;
+  set_active(db, mask);
+  for (int i = 0; i < 4; ++i) {
+    if (b->gvalid[i]) (void)hipGraphExecDestroy(b->gexec[i]);
+    b->gvalid[i] = false;
+  }
+  gprx::launch_center(db, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return GPRX_OK;
+}
+
 // Per-call settings of an evaluation: the context's distance mode, whether a predictive variance
 // is wanted, and the launch geometry from the context options and the batch size.
 void set_geometry(const gprx_ctx* c, DevBatch& db, bool want_var) {
@@ -596,6 +635,9 @@ int gprx_ctx_set_option(gprx_ctx* c, int option, int value) {
     case GPRX_OPT_GRAPHS:
       c->use_graphs = value != 0;
       return GPRX_OK;
+    case GPRX_OPT_ACTIVE_DIMS:
+      c->active_dims = value != 0;
+      return GPRX_OK;
     case GPRX_OPT_NODE_WAVES:
       if (value != 0 && value != 4 && value != 8) return set_err(c, GPRX_INVALID_ARGUMENT, "node waves: 0 (auto), 4 or 8");
       c->node_waves = value;
@@ -617,6 +659,7 @@ int gprx_ctx_kernel_stats(gprx_ctx* c, const char* kernel, double* total_ms, int
   std::lock_guard<std::mutex> g(c->mu);
   auto it = c->stats.find(kernel);
   KStat s = it == c->stats.end() ? KStat() : it->second;
+  if (!strcmp(kernel, "active_dims")) s.n = c->last_da;  // no kernel: the active dimension count, as launches
   if (total_ms) *total_ms = s.ms;
   if (launches) *launches = s.n;
   if (algo_flops) *algo_flops = s.flops;
@@ -734,8 +777,26 @@ int gprx_batch_set_train(gprx_batch* b, const double* X, int64_t xs, const doubl
       return rc;
     if ((rc = copy_in(c, db.Y + (size_t)s * db.Npad, Y + (size_t)s * ys, (size_t)db.N * sizeof(double), mem))) return rc;
   }
-  gprx::launch_center(db, c->stream);
-  HIPCHK(c, hipGetLastError());
+  // which dimensions are one constant in every slot: flags by slot and dimension, through grad_part
+  // (scratch of an evaluation) and the pinned h_out, read back under the synchronisation the copies
+  // need anyway
+  const int B = db.B, d = db.d;
+  int* h_flags = (int*)b->h_out;  // B x d ints <= B x (d + 3) doubles
+  if (c->active_dims) {
+    gprx::launch_const_flags(db, (int*)db.grad_part, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_flags, db.grad_part, (size_t)B * d * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  b->found_mask = 0;
+  for (int p = 0; p < d; ++p) {
+    bool varies = !c->active_dims;
+    for (int s = 0; s < B && !varies; ++s) varies = h_flags[(size_t)s * d + p] != 0;
+    if (varies) b->found_mask |= 1ull << p;
+  }
+  if (!b->found_mask) b->found_mask = 1;  // all constant: keep dimension 0
+  db.amask = 0;  // X changed: Xc is rewritten whatever the set
+  if ((rc = sync_active(b))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   b->have_train = true;
   b->factored = false;
@@ -836,6 +897,10 @@ int gprx_batch_run(gprx_batch* b, const double* theta, unsigned flags, double* m
   if (!b->have_train) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_run before gprx_batch_set_train");
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   DevBatch& db = b->db;
+  {
+    int rc = sync_active(b);
+    if (rc) return rc;
+  }
   set_geometry(c, db, var != nullptr);
   const int d = db.d, B = db.B, np = d + 2;
   // hyper-parameters -> kernel parameters on the device (derive_params: SEArd / GPE's
@@ -1058,6 +1123,10 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
     return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_optimize: bad options");
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   DevBatch& db = b->db;
+  {
+    int rc = sync_active(b);
+    if (rc) return rc;
+  }
   set_geometry(c, db, false);
   const int B = db.B, n = db.d + 2;
   gprx::LbArgs a{};

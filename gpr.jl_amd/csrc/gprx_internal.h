@@ -30,17 +30,21 @@ struct DevBatch {
                                // (default, set_geometry in gprx_api.hip: 4 for B >= 32, all nodes
                                // below that, where the 64 x 64 units leave most of the chip idle);
                                // larger: 64 x 64 core
-  int xs;                      // row stride of Xc: d | 1 (odd: spreads LDS banks)
+  int da;                      // active dimensions: those not constant over the training points of
+                               // every slot (gprx_batch_set_train; d when GPRX_OPT_ACTIVE_DIMS is 0 or
+                               // the distance mode is expanded).  A constant dimension adds an exact
+                               // +0 to every direct-mode distance, so the Gram and the gradient skip it
+  int xs;                      // row stride of Xc: da | 1 (odd: spreads LDS banks)
   int pst;                     // stride of params per slot
-  int gps;                     // stride of per-unit gradient partials (d + 2)
+  int gps;                     // stride of per-unit gradient partials (da + 2)
   int ngu;                     // gradient partial units per slot (lauum 4-tile units)
   int nlj;                     // lauum jobs per slot (units folded in pairs)
   int nimg;                    // largest number of point-tile images of a lauum unit (LDS size)
   size_t ld, mat;              // ld = Npad, mat = Npad*Npad
   double* X;                   // B x [Npad][d]   (column t = one CState, contiguous d values)
-  double* Xc;                  // B x [Npad][xs]  X minus its per-dimension mean over the N points,
-                               //                 dimensions d..xs-1 zero (theta-independent; the
-                               //                 gradient's distance sums)
+  double* Xc;                  // B x [Npad][xs]  the active dimensions of X, ascending, each minus its
+                               //                 mean over the N points, columns da..xs-1 zero
+                               //                 (theta-independent; the gradient's distance sums)
   double* Y;                   // B x Npad        (y - mean(X), zero padded)
   double* K;                   // B x mat: lower tiles of K as the Gram wrote them (kept: the gradient
                                //   reads its off-diagonal entries as Kf)
@@ -54,11 +58,12 @@ struct DevBatch {
   double* alpha;               // B x Npad        alpha = K^{-1} y; until k_alpha writes it, a block's
                                //                 working right-hand side (yw_slot)
   double* params;              // B x pst: [0,d) il2 = exp(-2 log ell), d: sf2, d+1: noise diag
-                               //          (sn2 + eps), d+2: sn2
+                               //          (sn2 + eps), d+2: sn2, d+3: the dropped dimensions' share of a distance sum
+                               //          (+0 or NaN, derive_params)
   double* theta;               // B x (d+2) hyper-parameters [log sn, log ell_1..d, log sf] of the
                                //          evaluation; params derive from it on the device
   double* logdet_part;         // B x nt          sum_r log L_rr per diagonal tile
-  double* grad_part;           // B x ngu x gps   per lauum unit: S_p (d), S_f, trace(W)
+  double* grad_part;           // B x ngu x gps   per lauum unit: S_p (da, active order), S_f, trace(W)
   double* Xs;                  // B x [Mpad][d]   test points
   double* KsT;                 // B x [Npad][Mpad] K*^T (column-major M x N, ld = Mpad)
   double* mu_part;             // B x nt x Mpad
@@ -71,6 +76,8 @@ struct DevBatch {
   int* lauum_order;            // nlj x 2 x LU: two units per job, long + short (lauum_plan)
   const int* active;           // B or null: evaluate only the slots with active[s] != 0 (the device
                                //   optimiser's rounds; null = every slot)
+  unsigned long long amask;    // bit p: dimension p is active (da bits; a mask, not a list: indexing a
+                               // list in the by-value struct would hold all of it in registers)
 };
 
 // GEMM operations of the recursive factorisation / inverse / prediction (tile units, see
@@ -249,6 +256,10 @@ __device__ __forceinline__ double wacc(double r, double a, double a2, double b, 
   return __builtin_fma(t * t, w, r);
 }
 
+// The place of active dimension p among the active ones, in ascending order: its column of Xc and
+// its entry of a gradient partial row.
+__device__ __forceinline__ int act_rank(unsigned long long amask, int p) { return __popcll(amask & ((1ull << p) - 1ull)); }
+
 // one lane's value on every lane (lane uniform); the sum over the wave's 64 lanes on every lane
 __device__ __forceinline__ double readlane_d(double v, int lane) {
   const long long b = __double_as_longlong(v);
@@ -279,7 +290,13 @@ __device__ inline void derive_params(const DevBatch& b, int slot) {
   const double sn2 = finite ? exp(2.0 * th[0]) : 1.0;
   P[d + 1] = sn2 + DBL_EPSILON;
   P[d + 2] = sn2;
-  P[d + 3] = 0.0;
+  // What the dropped (constant) dimensions add to every direct-mode distance sum, the value the
+  // Gram starts its sums from: +0, unless a scaled constant c sqrt(il2 / 2) overflows or is 0 * Inf;
+  // then c s - c s is NaN for every pair, as the sum over all dimensions would have it.
+  double r0 = 0.0;
+  for (int p = 0; p < d; ++p)
+    if (!((b.amask >> p) & 1) && !isfinite(b.X[(size_t)slot * b.Npad * d + p] * sqrt(0.5 * P[p]))) r0 = NAN;
+  P[d + 3] = r0;
   b.status[slot] = finite ? 0 : 2;
   b.info[slot] = 0;
 }
@@ -313,6 +330,8 @@ void set_lbfgs_attributes();   // gprx_lbfgs.hip, called by set_kernel_attribute
 void launch_params(const DevBatch& b, hipStream_t s);
 void launch_gram(const DevBatch& b, hipStream_t s);
 void launch_center(const DevBatch& b, hipStream_t s);
+// flags[B][d] (ints): 1 where dimension p of a slot is not one constant over its N training points
+void launch_const_flags(const DevBatch& b, int* flags, hipStream_t s);
 void launch_diag(const DevBatch& b, int jt, int upd, hipStream_t s);
 void launch_leaf(const DevBatch& b, int o, int n, int upd, hipStream_t s);
 // the first half of an 8-tile node (top leaf, TRSM, SYRK + TT) in one launch (k_node8; B >= 32)

@@ -43,15 +43,21 @@ namespace gprx {
 // a point in one bank (26-way conflicts on each ds_write_b64); 66 spreads them over the banks and
 // keeps the 16-B alignment of the inner loop's ds_read_b128.
 constexpr int CS = TS + 2;
+// (the waves per SIMD the registers must allow are stated: 8 in direct mode, 5 in expanded mode, which
+// the kernel met unasked until the active-dimension staging tipped the scheduler's estimate)
 template <int MODE>
-__global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
+__global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(MODE == 1 ? 8 : 5))) void k_gram(DevBatch db) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   __shared__ __attribute__((aligned(16))) double tab[128];  // exp_sf's sf2 2^(j/64) table (static: a
                                                             // known LDS address, no base add)
-  const int d = db.d, tid = threadIdx.x;
+  // Only the da active dimensions are staged and summed (DevBatch::da, amask; in ascending order, so
+  // the chain below keeps its order).  A dropped dimension holds one constant per slot: its scaled
+  // difference is an exact +0 and fma(0, 0, r) == r, so K keeps every bit.  Expanded mode runs with
+  // da == d, every dimension active (a^2 + b^2 - 2ab is no exact zero).
+  const int d = db.d, da = db.da, tid = threadIdx.x;
   double* xi = sm;
-  double* xj = xi + d * CS;
-  double* pw = xj + d * CS;
+  double* xj = xi + da * CS;
+  double* pw = xj + da * CS;
   int slot, t, i = 0, j = 0;
   if (!map_slot(db, db.ntl, slot, t)) return;
   {  // t-th lower tile in column-major order
@@ -72,9 +78,11 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
     const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(X, db.Npad * d * (int)sizeof(double));
     const int bi = i * TS * d * (int)sizeof(double), bj = j * TS * d * (int)sizeof(double);
     const int os = 8 * d * (int)sizeof(double);
-    for (int p = tid & 31; p < d; p += 32) {
+    for (int pf = tid & 31; pf < d; pf += 32) {  // pf: the dimension in X and P; p: its image row
+      if (!((db.amask >> pf) & 1)) continue;
+      const int p = act_rank(db.amask, pf);
       double vi[TS / 8], vj[TS / 8];
-      const int o0 = ((tid >> 5) * d + p) * (int)sizeof(double);
+      const int o0 = ((tid >> 5) * d + pf) * (int)sizeof(double);
 #pragma unroll
       for (int m = 0; m < TS / 8; ++m) {
         vi[m] = buffer_load_f64(xr, o0, bi + m * os);
@@ -83,7 +91,7 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
       // direct mode: coordinates pre-scaled by 1/(sqrt(2) ell_p) = sqrt(il2_p / 2), so that the
       // sums are r/2, the exponent's magnitude (0.5 il2_p is exact: as accurate as scaling by
       // 1/ell_p); each thread scales its own dimension (no staging barrier)
-      const double s = MODE == 1 ? sqrt(0.5 * P[p]) : 1.0;
+      const double s = MODE == 1 ? sqrt(0.5 * P[pf]) : 1.0;
 #pragma unroll
       for (int m = 0; m < TS / 8; ++m) {
         const int r = (tid >> 5) + 8 * m;
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
       }
     }
   }
-  for (int e = tid; e < d + 3; e += NTHR) pw[e] = P[e];
+  for (int e = tid; e < d + 4; e += NTHR) pw[e] = P[e];
   if (tid < 64) {  // sf2 (hi_j + lo_j) as hi + lo: the product's rounding error by fma, plus sf2 lo_j
     const double s2 = P[d], h = g_exp2tab[2 * tid], lo = g_exp2tab[2 * tid + 1];
     const double th = s2 * h;
@@ -108,14 +116,14 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) rr[a][b] = 0.0;
-  for (int p = 0; p < d; ++p) {
+  for (int p = 0; p < da; ++p) {
     const double2 u0 = *(const double2*)(xi + p * CS + 4 * rb);
     const double2 u1 = *(const double2*)(xi + p * CS + 4 * rb + 2);
     const double2 v0 = *(const double2*)(xj + p * CS + 4 * cb);
     const double2 v1 = *(const double2*)(xj + p * CS + 4 * cb + 2);
     const double av[4] = {u0.x, u0.y, u1.x, u1.y};
     const double bv[4] = {v0.x, v0.y, v1.x, v1.y};
-    const double w = pw[p];
+    const double w = pw[p];  // expanded mode only, where p is the dimension itself
     double a2[4], b2[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
@@ -133,6 +141,14 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
           rr[a][b] = __builtin_fma(t, t, rr[a][b]);
         }
       }
+  }
+  {  // the dropped dimensions' share of every sum (derive_params): +0, which leaves the sums (all
+     // >= +0) as they are, or NaN
+    const double r0 = pw[d + 3];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) rr[a][b] += r0;
   }
   double* K = db.K + (size_t)slot * db.mat;
   // buffer stores over the tile (base uniform): the lane's byte offset in a VGPR (column step
@@ -166,28 +182,32 @@ __global__ __launch_bounds__(NTHR) void k_gram(DevBatch db) {
   }
 }
 
-// Centred copy of the training points: Xc[t][p] = X[t][p] - mean_t X[t][p] for t < N, p < d, and 0
-// elsewhere (padded points, padded dimensions up to the stride xs).  grid = B, once per
-// gprx_batch_set_train.
+// Centred copy of the training points, active dimensions only: Xc[t][q] = X[t][p] - mean_t X[t][p],
+// p = act[q], for t < N, q < da, and 0 elsewhere (padded points, padded columns up to the stride
+// xs).  grid = B, once per gprx_batch_set_train.
 __global__ __launch_bounds__(NTHR) void k_center(DevBatch db) {
   __shared__ double mean[DMAX];
   __shared__ double red[4];
-  const int slot = blockIdx.x, tid = threadIdx.x, d = db.d, xs = db.xs;
+  __shared__ int act[DMAX];  // act[q]: the q-th active dimension
+  const int slot = blockIdx.x, tid = threadIdx.x, d = db.d, xs = db.xs, da = db.da;
   const double* X = db.X + (size_t)slot * db.Npad * d;
   double* Xc = db.Xc + (size_t)slot * db.Npad * xs;
-  for (int p = 0; p < d; ++p) {
+  if (tid < d && ((db.amask >> tid) & 1)) act[act_rank(db.amask, tid)] = tid;
+  __syncthreads();
+  for (int q = 0; q < da; ++q) {
+    const int p = act[q];
     double s = 0.0;
     for (int t = tid; t < db.N; t += NTHR) s += X[(size_t)t * d + p];
     s = wave_sum(s);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = s;
     __syncthreads();
-    if (tid == 0) mean[p] = (((red[0] + red[1]) + red[2]) + red[3]) / db.N;
+    if (tid == 0) mean[q] = (((red[0] + red[1]) + red[2]) + red[3]) / db.N;
   }
   __syncthreads();
   for (int e = tid; e < db.Npad * xs; e += NTHR) {
-    const int t = e / xs, p = e - t * xs;
-    Xc[e] = (t < db.N && p < d) ? X[(size_t)t * d + p] - mean[p] : 0.0;
+    const int t = e / xs, q = e - t * xs;
+    Xc[e] = (t < db.N && q < da) ? X[(size_t)t * d + act[q]] - mean[q] : 0.0;
   }
 }
 
@@ -506,7 +526,9 @@ __global__ __launch_bounds__(NTHR) void k_alpha(DevBatch db) {
 // with gi > gj are used, so the noise on the diagonal is never seen: G_rr uses sf2 analytically.
 //
 // The distance sums are expanded per wave tile (rows r, columns c):
-//   S_p = sum_r x_pr^2 R_r + sum_c x_pc^2 C_c - 2 sum_r x_pr Q_rp,   Q = G Xc  (64 x d)
+//   S_p = sum_r x_pr^2 R_r + sum_c x_pc^2 C_c - 2 sum_r x_pr Q_rp,   Q = G Xc  (64 x da)
+// over the da active dimensions only (DevBatch::da: a dimension that is constant has S_p = 0).  Each
+// S_p is its own MFMA column and its own reductions, so it does not depend on which others are there.
 // with R / C the row / column sums of G.  Q runs on the MFMA pipe with G straight from the
 // accumulators as the B operand (the swapped-operand C layout of mma_64x32_s1 is exactly a B
 // fragment), so the epilogue costs ~2d MFMAs + a few dozen cross-lane sums per wave instead of
@@ -561,7 +583,8 @@ __device__ __forceinline__ void lauum_body(const DevBatch& db) {
 }
 __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const int* ju) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int d = db.d, tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // d: the active dimensions (Xc's columns, the S_p of a partial row)
+  const int d = db.da, tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int xs = db.xs, xt = TS * xs;  // point-tile image: [64][xs]
   const int nimg = ju[1];
   double* sp = sm;                      // [4][SPW]
@@ -609,7 +632,7 @@ __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const i
   __syncthreads();
   GTS_D(gu, 5);
   if (active) {
-    const double sf2 = P[d];
+    const double sf2 = P[db.d];
     const int ir = ju[15 + w], ic = ju[19 + w];
     const double* xr = img + ir * xt;  // [r][xs]
     const double* xc = img + ic * xt;  // [c][xs]
@@ -837,7 +860,13 @@ __global__ __launch_bounds__(NTHR) void k_finalize(DevBatch db, int want_grad) {
     __shared__ double pr[4];
     const double* P = db.params + (size_t)slot * db.pst;
     const double* gp = db.grad_part + (size_t)slot * db.ngu * db.gps;
-    for (int q = 0; q < d + 2; ++q) {
+    // a partial row holds the S of the da active dimensions; a dropped (constant) dimension's
+    // distances are all 0 and so is its derivative, exactly (NaN where the distances are: P[d + 3])
+    const int da = db.da;
+    if (da < d)
+      for (int e = tid; e < d; e += NTHR) out[2 + e] = P[d + 3];  // ordered before thread 0's by the barriers below
+    int pn = 0;  // thread 0: the next dimension to look at
+    for (int q = 0; q < da + 2; ++q) {
       double tot = 0.0;
       for (int t = tid; t < db.ngu; t += NTHR) tot += gp[(size_t)t * db.gps + q];
       tot = wave_sum(tot);
@@ -846,8 +875,13 @@ __global__ __launch_bounds__(NTHR) void k_finalize(DevBatch db, int want_grad) {
       __syncthreads();
       if (tid == 0) {
         tot = ((pr[0] + pr[1]) + pr[2]) + pr[3];
-        if (q < d) out[2 + q] = P[q] * tot;       // d mll / d log ell_q = il2_q * S_q
-        else if (q == d) out[2 + d] = 2.0 * tot;  // d mll / d log sf     = 2 S_f
+        int p = 0;
+        if (q < da) {  // the q-th active dimension
+          while (pn < d - 1 && !((db.amask >> pn) & 1)) ++pn;
+          p = pn < d - 1 ? pn++ : pn;
+        }
+        if (q < da) out[2 + p] = P[p] * tot;       // d mll / d log ell_p = il2_p * S_p
+        else if (q == da) out[2 + d] = 2.0 * tot;  // d mll / d log sf     = 2 S_f
         else out[1] = P[d + 2] * tot;             // d mll / d log sn     = sn2 tr(W)
       }
     }
@@ -997,6 +1031,26 @@ __global__ __launch_bounds__(NTHR) void k_pred_final(DevBatch db) {
 }
 
 
+// Which dimensions of a slot are one constant: flags[slot][p] = 1 unless every training point t < N
+// holds the bits of the slot's first point in dimension p.  Mixed +0 / -0 differ in bits, and a
+// non-finite value never counts as constant (its difference is NaN, not 0).  grid = B, once per
+// gprx_batch_set_train; the host forms the batch's active list from the flags of all slots.
+__global__ __launch_bounds__(NTHR) void k_const_flags(DevBatch db, int* flags) {
+  __shared__ int nc[DMAX];
+  const int slot = blockIdx.x, tid = threadIdx.x, d = db.d;
+  const double* X = db.X + (size_t)slot * db.Npad * d;
+  if (tid < DMAX) nc[tid] = 0;
+  __syncthreads();
+  for (int e = tid; e < db.N * d; e += NTHR) {
+    const int p = e % d;
+    const double v = X[e];
+    if (__double_as_longlong(v) != __double_as_longlong(X[p]) || !isfinite(v)) nc[p] = 1;  // every writer stores 1
+  }
+  __syncthreads();
+  if (tid < d) flags[(size_t)slot * d + tid] = nc[tid];
+}
+// (defined here: non-template kernels land in the code object in definition order)
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -1024,8 +1078,8 @@ void set_kernel_attributes() {
 }
 
 void launch_gram(const DevBatch& b, hipStream_t s) {
-  if (b.dist_mode == 0) hipLaunchKernelGGL(k_gram<0>, dim3(grid_blocks(b.B, b.ntl)), dim3(NTHR), gram_lds(b.d), s, b);
-  else hipLaunchKernelGGL(k_gram<1>, dim3(grid_blocks(b.B, b.ntl)), dim3(NTHR), gram_lds(b.d), s, b);
+  if (b.dist_mode == 0) hipLaunchKernelGGL(k_gram<0>, dim3(grid_blocks(b.B, b.ntl)), dim3(NTHR), gram_lds(b.da), s, b);
+  else hipLaunchKernelGGL(k_gram<1>, dim3(grid_blocks(b.B, b.ntl)), dim3(NTHR), gram_lds(b.da), s, b);
 }
 __global__ __launch_bounds__(64) void k_params(DevBatch b) {
   const int slot = blockIdx.x * 64 + threadIdx.x;
@@ -1033,6 +1087,9 @@ __global__ __launch_bounds__(64) void k_params(DevBatch b) {
 }
 void launch_params(const DevBatch& b, hipStream_t s) { hipLaunchKernelGGL(k_params, dim3((b.B + 63) / 64), dim3(64), 0, s, b); }
 void launch_center(const DevBatch& b, hipStream_t s) { hipLaunchKernelGGL(k_center, dim3(b.B), dim3(NTHR), 0, s, b); }
+void launch_const_flags(const DevBatch& b, int* flags, hipStream_t s) {
+  hipLaunchKernelGGL(k_const_flags, dim3(b.B), dim3(NTHR), 0, s, b, flags);
+}
 void launch_diag(const DevBatch& b, int jt, int upd, hipStream_t s) {
   hipLaunchKernelGGL(k_diag_f, dim3(b.B), dim3(NTHR), 0, s, b, jt, upd);
 }
