@@ -50,7 +50,6 @@ struct gprx_ctx {
   // recursion nodes of <= this many tiles use the 64 x 32 pair-unit GEMM; 0 = auto (set_geometry:
   // 4 for batches of >= 32 slots, every node below that) (GPRX_OPT_SMALL_N)
   int small_n = 0;
-  int node_waves = 0;  // GPRX_OPT_NODE_WAVES: 0 auto, 8 (k_node8), 4 (k_node8h)
   // replay each batch's launch sequence as a hipGraph (GPRX_OPT_GRAPHS).  Off by default: measured
   // equal to direct launches at B=1..192 (the launches are queued far ahead of the GPU).
   bool use_graphs = false;
@@ -96,7 +95,7 @@ struct gprx_batch {
   // captured evaluation graphs, one per (want_grad, want_pred); valid while the key matches
   hipGraphExec_t gexec[4] = {};
   DevBatch gkey[4];
-  int gkey_ctx[4][3] = {};
+  int gkey_ctx[4][2] = {};
   bool gvalid[4] = {};
 };
 
@@ -355,12 +354,8 @@ void factor_block(gprx_ctx* c, hipStream_t st, const DevBatch& db, int o, int n,
   }
   if (n == 8 && leaf == 4 && db.B >= 32) {  // the whole node in one launch (k_node8)
     const double m = 4 * T;
-    // the 4-wave form (two slots per CU, bit-identical) on request only: measured slower at every
-    // batch size ("Two slots per CU"): a paired slot's fp64 VALU chain and MFMAs share
-    // the SIMD's one fp64 pipe with the other slot's, so the pair runs at half speed
-    const bool four = c->node_waves == 4;
-    timed(c, st, four ? "node8h" : "node8", Bd * (4.0 * m * m * m / 3.0 + 4.0 * m * m * m),
-          Bd * 8.0 * (16.0 * m * m + 6.5 * m * m), [&] { gprx::launch_node8(db, o, upd, st, four); }, n);
+    timed(c, st, "node8", Bd * (4.0 * m * m * m / 3.0 + 4.0 * m * m * m), Bd * 8.0 * (16.0 * m * m + 6.5 * m * m),
+          [&] { gprx::launch_node8(db, o, upd, st); }, n);
     return;
   }
   if (n == 1) {
@@ -438,8 +433,7 @@ int run_graph(gprx_batch* b, bool want_grad, bool want_pred) {
   const DevBatch& db = b->db;
   const int gi = (want_grad ? 1 : 0) + (want_pred ? 2 : 0);
   const bool same = b->gvalid[gi] && memcmp(&b->gkey[gi], &db, sizeof(DevBatch)) == 0 &&
-                    b->gkey_ctx[gi][0] == c->leaf_tiles && b->gkey_ctx[gi][1] == c->small_n &&
-                    b->gkey_ctx[gi][2] == c->node_waves;
+                    b->gkey_ctx[gi][0] == c->leaf_tiles && b->gkey_ctx[gi][1] == c->small_n;
   if (!same) {
     if (b->gvalid[gi]) (void)hipGraphExecDestroy(b->gexec[gi]);
     b->gvalid[gi] = false;
@@ -458,7 +452,6 @@ int run_graph(gprx_batch* b, bool want_grad, bool want_pred) {
     memcpy(&b->gkey[gi], &db, sizeof(DevBatch));
     b->gkey_ctx[gi][0] = c->leaf_tiles;
     b->gkey_ctx[gi][1] = c->small_n;
-    b->gkey_ctx[gi][2] = c->node_waves;
     b->gvalid[gi] = true;
   }
   HIPCHK(c, hipGraphLaunch(b->gexec[gi], c->stream));
@@ -637,10 +630,6 @@ int gprx_ctx_set_option(gprx_ctx* c, int option, int value) {
       return GPRX_OK;
     case GPRX_OPT_ACTIVE_DIMS:
       c->active_dims = value != 0;
-      return GPRX_OK;
-    case GPRX_OPT_NODE_WAVES:
-      if (value != 0 && value != 4 && value != 8) return set_err(c, GPRX_INVALID_ARGUMENT, "node waves: 0 (auto), 4 or 8");
-      c->node_waves = value;
       return GPRX_OK;
   }
   return set_err(c, GPRX_INVALID_ARGUMENT, "unknown option");

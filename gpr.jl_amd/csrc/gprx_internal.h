@@ -334,9 +334,8 @@ void launch_center(const DevBatch& b, hipStream_t s);
 void launch_const_flags(const DevBatch& b, int* flags, hipStream_t s);
 void launch_diag(const DevBatch& b, int jt, int upd, hipStream_t s);
 void launch_leaf(const DevBatch& b, int o, int n, int upd, hipStream_t s);
-// the first half of an 8-tile node (top leaf, TRSM, SYRK + TT) in one launch (k_node8; B >= 32)
-// four: the 4-wave form (k_node8h, two slots per CU; bit-identical results)
-void launch_node8(const DevBatch& b, int o, int upd, hipStream_t s, bool four = false);  // a whole 8-tile node (k_node8)
+// a whole 8-tile node (top leaf, TRSM, SYRK + TT, bottom leaf, LINV21) in one launch (k_node8; B >= 32)
+void launch_node8(const DevBatch& b, int o, int upd, hipStream_t s);
 // one launch; with g2.op != OP_NONE the units of g2 are appended to g's (independent ops)
 void launch_gemm(const DevBatch& b, const GemmGeom& g, hipStream_t s, const GemmGeom& g2 = GemmGeom{OP_NONE, 0, 0, 0});
 // around a block [o, o + n): its right-hand side Yw before it, its rows of z after it

@@ -1070,7 +1070,6 @@ void set_kernel_attributes() {
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cross_lds(DMAX));
   for (const void* f : {(const void*)k_leaf9, (const void*)k_node8})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)leaf9_lds_bytes());
-  (void)hipFuncSetAttribute((const void*)k_node8h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)leaf4_lds_bytes());
   for (const void* f : {(const void*)k_gemm<REV_A>, (const void*)k_gemm<REV_B>, (const void*)k_gemm<TRI_A_FIRST>})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)linv21_lds_bytes());
   set_lbfgs_attributes();
@@ -1100,9 +1099,8 @@ void launch_leaf(const DevBatch& b, int o, int n, int upd, hipStream_t s) {
   }
   hipLaunchKernelGGL(k_leaf, dim3(b.B), dim3(NTHR), 0, s, b, o, n, upd);
 }
-void launch_node8(const DevBatch& b, int o, int upd, hipStream_t s, bool four) {
-  if (four) hipLaunchKernelGGL(k_node8h, dim3(b.B), dim3(NTHR), leaf4_lds_bytes(), s, b, o, upd);
-  else hipLaunchKernelGGL(k_node8, dim3(b.B), dim3(2 * NTHR), leaf9_lds_bytes(), s, b, o, upd);
+void launch_node8(const DevBatch& b, int o, int upd, hipStream_t s) {
+  hipLaunchKernelGGL(k_node8, dim3(b.B), dim3(2 * NTHR), leaf9_lds_bytes(), s, b, o, upd);
 }
 void launch_gemm(const DevBatch& b, const GemmGeom& g, hipStream_t s, const GemmGeom& g2) {
   if (g.op != OP_PREDVAR && g.n <= b.small_n) {  // small node: pair units, 64 x 32 waves

@@ -73,7 +73,7 @@ __device__ __forceinline__ void wave_ts(int o, int slot, int ev) {
   }
 }
 #define W_TS(ev) wave_ts(o, slot, ev)
-// whole-node kernels (k_node8 / k_node8h): thread 0 stamps phase ev of slot's node launch (region
+// the whole-node kernel (k_node8): thread 0 stamps phase ev of slot's node launch (region
 // 0 from entry 2^19: 8 per slot: start, after the top leaf, TRSM, SYRK + TT, the bottom leaf, end,
 // then the hardware CU id and XCC id)
 __device__ __forceinline__ void node_ts(int slot, int ev) {

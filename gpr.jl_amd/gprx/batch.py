@@ -48,7 +48,7 @@ class Context:
 
     def set_option(self, option: int, value: int):
         """Launch-geometry option (gprx_ctx_set_option: L.OPT_LEAF_TILES / OPT_SMALL_N / OPT_GRAPHS);
-        results are identical under every setting."""
+        results are identical under every setting.  Id 4 is retired: "unknown option"."""
         L.check(L.lib.gprx_ctx_set_option(self.h, int(option), int(value)), self.h)
 
     def set_profiling(self, enable: bool):

@@ -103,9 +103,6 @@ int gprx_ctx_set_profiling(gprx_ctx* ctx, int enable);
  *                        kernel; 1: every 64 x 64 diagonal tile on its own; 0 (default) = auto
  *   GPRX_OPT_SMALL_N     recursion nodes of <= value tiles use the 64 x 32 pair-unit GEMM; 0 = auto
  *   GPRX_OPT_GRAPHS      1: replay each evaluation's launch sequence as a hipGraph (default 0)
- *   GPRX_OPT_NODE_WAVES  the whole-8-tile-node kernel (batches >= 32 slots): 8 = one 8-wave
- *                        workgroup per slot (0, the default, is 8); 4 = a 4-wave workgroup per
- *                        slot, two slots per CU (measured slower on MI355X)
  *   GPRX_OPT_ACTIVE_DIMS 1 (default): gprx_batch_set_train finds the input dimensions that hold one
  *                        constant over the training points of every slot, and direct-mode
  *                        evaluations leave them out of the Gram and the gradient (their distances
@@ -115,7 +112,7 @@ int gprx_ctx_set_profiling(gprx_ctx* ctx, int enable);
 #define GPRX_OPT_LEAF_TILES 1
 #define GPRX_OPT_SMALL_N 2
 #define GPRX_OPT_GRAPHS 3
-#define GPRX_OPT_NODE_WAVES 4
+/* id 4 is retired (a launch form that no longer exists) and not reused: GPRX_INVALID_ARGUMENT */
 #define GPRX_OPT_ACTIVE_DIMS 5
 int gprx_ctx_set_option(gprx_ctx* ctx, int option, int value);
 int gprx_ctx_kernel_stats(gprx_ctx* ctx, const char* kernel, double* total_ms, int64_t* launches,

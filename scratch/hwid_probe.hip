@@ -1,5 +1,5 @@
 // Which SIMD does wave w of a workgroup land on, and which workgroups share a CU?  B blocks of 256
-// threads with 68 KB of dynamic LDS (k_node8h's shape); every wave records its hardware ids and
+// threads with 68 KB of dynamic LDS; every wave records its hardware ids and
 // realtime stamps around a ~40 us busy loop.  hipcc --offload-arch=gfx950 -O3 hwid_probe.hip -o hwid_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>

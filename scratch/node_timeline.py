@@ -1,7 +1,7 @@
-"""Phase timeline of the whole-8-tile-node kernels (k_node8: 8 waves, k_node8h: 4 waves) on one
-batch, from a stamps build (scratch/varbuild.sh nstamps ../gpr.jl_amd/csrc/gprx_kernels.hip -DGPRX_STAMPS):
+"""Phase timeline of the whole-8-tile-node kernel (k_node8) on one batch, from a stamps build
+(scratch/varbuild.sh nstamps ../gpr.jl_amd/csrc/gprx_kernels.hip -DGPRX_STAMPS):
     GPRX_LIB=scratch/var/libgprx_nstamps.so python scratch/node_timeline.py MECH N KEY G TRIALS
-Per form: median phase durations per slot (us) and, per CU, how many slots overlap in time."""
+Median phase durations per slot (us) and, per CU, how many slots overlap in time."""
 import collections
 import ctypes as C
 import pathlib
@@ -27,31 +27,28 @@ th = np.tile(data.theta0(mech, key), (B, 1))
 ctx = gprx.Context(0)
 b = gprx.GPBatch(B, d, N, 0, ctx=ctx)
 b.set_train(X, Y)
-for w in (8, 4):
-    ctx.set_option(L.OPT_NODE_WAVES, w)
-    for _ in range(2):
-        b.run(th, grad=False)
-    assert f(0, None, 0, 1) == 0
+for _ in range(2):
     b.run(th, grad=False)
-    buf = np.zeros(524288 + 32768 * 8, dtype=np.uint64)
-    assert f(0, buf.ctypes.data, buf.size, 0) == 0
-    st = buf[524288:524288 + B * 8].reshape(B, 8)
-    t = st[:, :6].astype(np.float64) / 100.0  # us
-    dur = np.diff(t, axis=1)
-    names = ["leaf_top", "trsm", "syrk_tt", "leaf_bot", "linv21"]
-    med = {n: round(float(np.median(dur[:, i])), 1) for i, n in enumerate(names)}
-    tot = t[:, 5] - t[:, 0]
-    hw, xcc = st[:, 6], st[:, 7]
-    cu = [(int(xcc[s]) & 15, int(hw[s] >> 13) & 7, int(hw[s] >> 12) & 1, int(hw[s] >> 8) & 15) for s in range(B)]
-    by = collections.defaultdict(list)
-    for s in range(B):
-        by[cu[s]].append((t[s, 0], t[s, 5], s))
-    ov = collections.Counter()
-    for k, v in by.items():
-        for i, (a0, a1, _) in enumerate(v):
-            ov[sum(1 for (b0, b1, _) in v if b0 < a1 and a0 < b1) - 1] += 1
-    span = (t[:, 5].max() - t[:, 0].min())
-    print(f"waves={w} B={B}: per-slot median {med}, node {np.median(tot):.1f} us (p10 {np.percentile(tot, 10):.1f}, "
-          f"p90 {np.percentile(tot, 90):.1f}); launch span {span:.1f} us; CUs {len(by)}; slots overlapping k others: "
-          f"{dict(sorted(ov.items()))}", flush=True)
-ctx.set_option(L.OPT_NODE_WAVES, 0)
+assert f(0, None, 0, 1) == 0
+b.run(th, grad=False)
+buf = np.zeros(524288 + 32768 * 8, dtype=np.uint64)
+assert f(0, buf.ctypes.data, buf.size, 0) == 0
+st = buf[524288:524288 + B * 8].reshape(B, 8)
+t = st[:, :6].astype(np.float64) / 100.0  # us
+dur = np.diff(t, axis=1)
+names = ["leaf_top", "trsm", "syrk_tt", "leaf_bot", "linv21"]
+med = {n: round(float(np.median(dur[:, i])), 1) for i, n in enumerate(names)}
+tot = t[:, 5] - t[:, 0]
+hw, xcc = st[:, 6], st[:, 7]
+cu = [(int(xcc[s]) & 15, int(hw[s] >> 13) & 7, int(hw[s] >> 12) & 1, int(hw[s] >> 8) & 15) for s in range(B)]
+by = collections.defaultdict(list)
+for s in range(B):
+    by[cu[s]].append((t[s, 0], t[s, 5], s))
+ov = collections.Counter()
+for k, v in by.items():
+    for i, (a0, a1, _) in enumerate(v):
+        ov[sum(1 for (b0, b1, _) in v if b0 < a1 and a0 < b1) - 1] += 1
+span = (t[:, 5].max() - t[:, 0].min())
+print(f"B={B}: per-slot median {med}, node {np.median(tot):.1f} us (p10 {np.percentile(tot, 10):.1f}, "
+      f"p90 {np.percentile(tot, 90):.1f}); launch span {span:.1f} us; CUs {len(by)}; slots overlapping k others: "
+      f"{dict(sorted(ov.items()))}", flush=True)

@@ -380,6 +380,13 @@ def test_factorisation_paths_match_golden(gprx, golden_dir, leaf, small_n):
         c.close()
 
 
+def test_retired_option_id_is_unknown(gprx, ctx):
+    """Id 4 selected a launch form that no longer exists (the 4-wave node); it is not reused."""
+    with pytest.raises(gprx.GPRXError, match="unknown option") as e:
+        ctx.set_option(4, 4)
+    assert e.value.status == 2  # GPRX_INVALID_ARGUMENT
+
+
 def test_fused_node_failure_isolated(gprx, ctx):
     """The fused 8-tile node (k_node8: top leaf + TRSM + SYRK+TT + bottom leaf + LINV21 in one launch)
     at B = 32, N = 512: a slot whose point p has NaN coordinates fails at pivot p + 1 (dpotf2's
@@ -410,44 +417,40 @@ def test_fused_node_failure_isolated(gprx, ctx):
     b.close()
 
 
-@pytest.mark.parametrize("N,B,mech", [(512, 64, "CP"), (1024, 40, "P2"), (500, 36, "P2"), (2048, 32, "P2")])
-def test_node8_four_wave_form_bit_identical(gprx, ctx, N, B, mech):
-    """The 4-wave form of the whole-8-tile-node kernel (k_node8h: two slots per CU, one inverse
-    image, the chain on all four waves, parked inverse items, z partials in S's free upper tile)
-    gives k_node8's results bit for bit: LML, gradient, mean, variance, status and failing pivot,
-    including a failing slot (NaN point: pivot 101 in the top leaf, 301 in the bottom leaf) and the
-    nodes an ancestor's SYRK updated (N = 1024, 2048: nodes read from S); N = 500 pads the last
-    tile.  So the form is a launch choice only (GPRX_OPT_NODE_WAVES)."""
-    from gprx import _lib as L, data
+@pytest.fixture(scope="module")
+def node8_golden(golden_dir):
+    import importlib.util
 
-    G = 26 if mech == "CP" else 6
-    trs = [data.make_trial(mech, N, 40, seed=data.trial_seed(mech, 60 + t)) for t in range(B // G + 1)]
-    X = np.stack([trs[s // G]["X"] for s in range(B)])
-    Y = np.stack([(trs[s // G]["Xcurr"] if mech == "CP" else trs[s // G]["Y"])[s % G] for s in range(B)])
-    Xs = np.stack([trs[s // G]["Xs"] for s in range(B)])
-    X[3][:, 100] = np.nan
-    X[B - 2][:, 300] = np.nan
-    rng = np.random.default_rng(N + B)
-    th0 = data.theta0(mech, 512)
-    T = np.stack([th0 + 0.05 * rng.standard_normal(th0.shape[0]) for _ in range(B)])
-    b = gprx.GPBatch(B, 26, N, 40, ctx=ctx)
-    b.set_train(X, Y)
-    b.set_test(Xs)
-    out = {}
-    try:
-        for w in (8, 4):
-            ctx.set_option(L.OPT_NODE_WAVES, w)
-            out[w] = b.run(T, grad=True, predict=True)
-    finally:
-        ctx.set_option(L.OPT_NODE_WAVES, 0)
-    assert out[4]["status"][3] == 1 and out[4]["info"][3] == 101
-    assert out[4]["status"][B - 2] == 1 and out[4]["info"][B - 2] == 301
-    assert np.sum(out[4]["status"] == 0) == B - 2
-    for k in ("mll", "grad", "mu", "var", "status", "info"):
-        np.testing.assert_array_equal(out[4][k], out[8][k], err_msg=k)
-    ok = np.nonzero(out[4]["status"] == 0)[0]
-    check_slot(out[4], int(ok[0]), X[ok[0]], Y[ok[0]], T[ok[0]], Xs[ok[0]], ctx.dist_mode, strict=mech != "CP")
-    b.close()
+    spec = importlib.util.spec_from_file_location("make_golden_node8", golden_dir / "make_golden_node8.py")
+    make = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make)
+    with np.load(golden_dir / "node8_parent.npz") as f:
+        return make, {k: f[k] for k in f.files}
+
+
+@pytest.mark.parametrize("N,B,mech", [(512, 64, "CP"), (1024, 40, "P2"), (500, 36, "P2"), (2048, 32, "P2")])
+def test_node8_matches_recorded_results(gprx, ctx, node8_golden, N, B, mech):
+    """The whole-8-tile-node kernel (k_node8) and everything around it against results recorded on
+    an MI355X from commit 58cbc88 (tests/golden/node8_parent.npz, by tests/golden/make_golden_node8.py,
+    whose make_case builds the inputs here too): LML, gradient, mean, variance, status and failing
+    pivot of every slot bit for bit, including a failing slot (NaN point: pivot 101 in the top leaf,
+    301 in the bottom leaf) and the nodes an ancestor's SYRK updated (N = 1024, 2048: nodes read
+    from S); N = 500 pads the last tile.  Two runs of the batch agree bit for bit, and the first good
+    slot agrees with the oracle.  The inputs' digest is checked first: a host whose generator rounds
+    differently has other inputs, not another kernel."""
+    make, rec = node8_golden
+    assert (N, B, mech) in make.CASES
+    X, Y, Xs, T = make.make_case(N, B, mech)
+    assert make.digest(X, Y, Xs, T) == str(rec[make.key(N, B, mech, "sha256")]), "inputs differ from the recorded ones"
+    r1, r2 = make.run_case(gprx, ctx, X, Y, Xs, T)
+    assert r1["status"][3] == 1 and r1["info"][3] == 101
+    assert r1["status"][B - 2] == 1 and r1["info"][B - 2] == 301
+    assert np.sum(r1["status"] == 0) == B - 2
+    for k in make.OUTPUTS:
+        assert make.same_bits(r1[k], r2[k]), f"{k}: two runs differ"
+        assert make.same_bits(r1[k], rec[make.key(N, B, mech, k)]), f"{k}: differs from the recorded result"
+    ok = np.nonzero(r1["status"] == 0)[0]
+    check_slot(r1, int(ok[0]), X[ok[0]], Y[ok[0]], T[ok[0]], Xs[ok[0]], ctx.dist_mode, strict=mech != "CP")
 
 
 def test_production_path_b32_full_size(gprx, ctx):

@@ -47,7 +47,7 @@ def _runs():
 
 RUNS = _runs()
 RUN_IDS = [f"{n}-B{B}" if B else n for n, B in RUNS]
-OPTION_RUNS = [(n, B, o) for n, B in RUNS if n[0] in "cd" for o in (("graphs",) + (("node_waves4",) if n[0] == "d" else ()))]
+OPTION_RUNS = [(n, B, "graphs") for n, B in RUNS if n[0] in "cd"]
 
 
 @pytest.fixture(scope="module")
@@ -168,13 +168,13 @@ def test_cov_diagonal_agrees_with_variance(gprx, ctx, name, B, mode):
 
 @pytest.mark.parametrize("name,B,option", OPTION_RUNS, ids=[f"{n}-{o}" for n, _, o in OPTION_RUNS])
 def test_launch_options_are_bit_equal(gprx, ctx, name, B, option):
-    """Captured graphs and the 4-wave form of the 8-tile node are launch choices only."""
+    """Captured graphs are a launch choice only."""
     from gprx import _lib as L
 
     dev = device(gprx, ctx, name, B, 1)
     c = gprx.Context(0)
     try:
-        c.set_option(*((L.OPT_GRAPHS, 1) if option == "graphs" else (L.OPT_NODE_WAVES, 4)))
+        c.set_option(L.OPT_GRAPHS, 1)
         got = evaluate(gprx, c, fixture(name), B, 1)
     finally:
         c.close()
