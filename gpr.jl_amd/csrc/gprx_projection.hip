@@ -681,6 +681,17 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
 }  // namespace
 
 // ---- projectv! for T independent mechanism states: one wave each ------------------------------
+// Contract (include/gprx.h, gprx_projectv): status 1 and a NaN row for an exactly singular KKT
+// matrix.  A non-finite system (|w| beyond 2/dt: sqrt of a negative number) is NOT detected --
+// project<NW> has no finiteness test, unlike vi_newton: NaN compares false in the pivot search, in
+// the zero-pivot test and in the convergence test, so the state runs all a.iters iterations and
+// returns a NaN row with iterations = a.iters and status 0.  With NaNs the butterfly's pivot row p
+// may differ from lane to lane.  On the lanes l < n, the only ones that touch A, it stays below n;
+// a lane l >= n may end with p >= n, but it swaps nothing, and readlane of a lane <= 63 is valid.
+// The state's wave touches no other state's memory.
+// This holds for k_project (NW = 1), where it is measured.  It is not a statement about the
+// rollouts: in project<4> a lane-dependent p makes `if (p != k) pj_sync<NW>()` a barrier inside
+// divergent control flow, and no test gives k_rollout_max a non-finite state.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_project(ProjArgs a) {
   __shared__ PState P;
   const int t = blockIdx.x, l = threadIdx.x;

@@ -302,7 +302,16 @@ int gprx_rollout_min(gprx_ctx* ctx, int mech, int usesin, double dt, int steps, 
  * w_nb).  Outputs vw_out (the projected twists; NaN for a failed state), iterations[t], status[t]
  * (0 ok, 1 singular KKT matrix: Julia's F \ f throws SingularException).  mech: GPRX_MECH_*, the
  * experiment mechanisms of examples/utils/data/simulations.jl (P1 pendulum, P2 double pendulum,
- * CP cart-pole, FB four-bar).  dt: mechanism.dt (0.01 in the experiments).                       */
+ * CP cart-pole, FB four-bar).  dt: mechanism.dt (0.01 in the experiments).
+ * newton_iter = 0 returns vw_pred unchanged (iterations 0, status 0); eps = 0 runs all newton_iter
+ * iterations.  Status 0 does not say that the iteration converged: compare iterations[t] with
+ * newton_iter.  A state whose system is not finite (|w| of a body or of its prediction beyond
+ * 2/dt, where the reference's sqrt throws a DomainError) is not detected, unlike in
+ * gprx_vi_step: it runs all newton_iter iterations on NaNs and returns a NaN row with
+ * iterations[t] = newton_iter and status[t] = 0 (measured on an MI355X, asserted by
+ * tests/test_hp_physics.py).  The other states of the launch are not affected by it.  This is
+ * gprx_projectv's contract alone: what gprx_rollout_max and gprx_rollout_max_md do with such a
+ * state in their projection is neither specified nor tested.                                     */
 int gprx_projectv(gprx_ctx* ctx, int mech, double dt, int T, const double* cstates, const double* vw_pred,
                   double regularizer, int newton_iter, double eps, double* vw_out, int* iterations, int* status);
 /* One variational-integrator step, ConstrainedDynamics 0.7.4 newton!(mechanism) after
