@@ -1567,6 +1567,82 @@ int gprx_vi_step(gprx_ctx* c, int mech, double dt, int T, const double* cstates,
                                    [](gprx::ViArgs& a, const double*) { a.grav = 9.81; });  // |mechanism.g| (simulations.jl; gprx/vi.py GRAV)
 }
 
+// simulate!(mechanism, steps dt, control!, record = true) of the datasets (examples/utils/data/
+// simulations.jl:7-213; examples/parallel/dataframes.jl:58-93 reads the storage at the sampled
+// indices) for T trajectories: k_simulate in launches of at most steps_per_launch steps, so that no
+// launch runs for seconds; the device buffer [cs | mass | inertia | damp | rec | out | cursor |
+// status] carries state, record cursor and status from one launch to the next.
+int gprx_simulate(gprx_ctx* c, int mech, double dt, int steps, int T, const double* start, const double* mass,
+                  const double* inertia, const double* damp, double vi_regularizer, int newton_iter, double eps, int R,
+                  const int* rec, int steps_per_launch, double* out, int* status) {
+  if (!c) return GPRX_INVALID_ARGUMENT;
+  const std::string fn = "gprx_simulate";
+  gprx::SimArgs a{};
+  if (!build_mech(mech, a.mech) || steps < 0 || T < 0 || R < 1 || newton_iter < 0 || steps_per_launch < 0 || !(dt > 0.0) ||
+      !std::isfinite(vi_regularizer) || !(eps >= 0.0))
+    return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / steps / T / R / newton_iter / steps_per_launch / dt / regularizer / eps");
+  if (T == 0) return GPRX_OK;
+  if (!start || !rec || !out) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  int last = 1;  // the largest index wanted: no trajectory steps past it
+  for (int t = 0; t < T; ++t)
+    for (int r = 0; r < R; ++r) {
+      const int j = rec[(size_t)t * R + r];
+      if (j < 1 || j > steps + 1 || (r > 0 && j < rec[(size_t)t * R + r - 1]))
+        return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": rec must be non-decreasing per trajectory, in [1, steps + 1]");
+      last = j > last ? j : last;
+    }
+  // The default bounds a launch whose every step runs all newton_iter = 100 iterations (a solve whose twist
+  // does not settle; a stagnated one ends sooner, k_simulate): a four-bar step then takes 12 ms with 200
+  // trajectories in flight (measured), 16 of them 0.19 s.  One wave per trajectory: beyond about
+  // 1024 trajectories the waves no longer run side by side and a launch grows with T, so the default shrinks.
+  const int spl = steps_per_launch > 0 ? steps_per_launch : (T <= 16 * 1024 ? 16 / ((T + 1023) / 1024) : 1);
+  std::lock_guard<std::mutex> g(c->mu);
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const size_t nb = a.mech.nb, n_cs = (size_t)T * 13 * nb, n_rec = (size_t)T * R, n_out = n_rec * 13 * nb;
+  Layout l;
+  const size_t o_cs = l.take<double>(n_cs), o_m = l.take<double>(mass ? T * nb : 0), o_J = l.take<double>(inertia ? T * nb * 9 : 0),
+               o_c = l.take<double>(damp ? T * nb * 6 : 0), o_rec = l.take<int>(n_rec), o_out = l.take<double>(n_out),
+               o_cur = l.take<int>(T), o_st = l.take<int>(T);
+  char* base;
+  int rc = ctx_scratch(c, l.size, &base);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(base + o_cs, start, n_cs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (mass) HIPCHK(c, hipMemcpyAsync(base + o_m, mass, T * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (inertia) HIPCHK(c, hipMemcpyAsync(base + o_J, inertia, T * nb * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (damp) HIPCHK(c, hipMemcpyAsync(base + o_c, damp, T * nb * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + o_rec, rec, n_rec * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(base + o_cur, 0, (size_t)T * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(base + o_st, 0, (size_t)T * sizeof(int), c->stream));
+  a.dt = dt;
+  a.reg = vi_regularizer;
+  a.eps = eps;
+  a.grav = 9.81;  // |mechanism.g| (simulations.jl:10, :110; gprx/vi.py GRAV)
+  a.iters = newton_iter;
+  a.T = T;
+  a.R = R;
+  a.mass = mass ? at<double>(base, o_m) : nullptr;
+  a.inertia = inertia ? at<double>(base, o_J) : nullptr;
+  a.damp = damp ? at<double>(base, o_c) : nullptr;
+  a.rec = at<int>(base, o_rec);
+  a.cs = at<double>(base, o_cs);
+  a.cursor = at<int>(base, o_cur);
+  a.status = at<int>(base, o_st);
+  a.out = at<double>(base, o_out);
+  const int total = last - 1;  // steps any trajectory takes
+  a.step0 = 0;
+  do {  // at least one launch: index 1 is recorded without a step
+    a.nsteps = total - a.step0 < spl ? total - a.step0 : spl;
+    timed(c, c->stream, "simulate", 0.0, 0.0, [&] { gprx::launch_simulate(a, c->stream); });
+    HIPCHK(c, hipGetLastError());
+    a.step0 += a.nsteps;
+  } while (a.step0 < total);
+  HIPCHK(c, hipMemcpyAsync(out, base + o_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, base + o_st, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  return GPRX_OK;
+}
+
 // ---- rollout in minimal coordinates ------------------------------------------------------------
 // gprx_rollout_min (vi_regularizer null: MeanZero GPs, k_rollout<., RolloutArgs>) and
 // gprx_rollout_min_md (predictdynamicsmin with MeanDynamics GPs, examples/utils/predictdynamics.jl:

@@ -225,8 +225,27 @@ struct ViArgs {
   int* iters_out;     // T Newton iterations
   int* status;        // T: 0 converged, 1 not converged, 2 failed (non-finite / singular system)
 };
+// Many variational-integrator steps per launch with per-trajectory bodies and viscous friction (the
+// datasets' simulate!, examples/utils/data/simulations.jl): steps [step0, step0 + nsteps) of every
+// trajectory.  cs, cursor and status carry a trajectory from one launch to the next.
+struct SimArgs {
+  MechDev mech;         // the joints; its m / J are the bodies where mass / inertia are null
+  double dt, reg, eps, grav;
+  int iters;            // newtonIter
+  int T, R;             // trajectories, records per trajectory
+  int step0, nsteps;    // cs holds storage index step0 + 1 on entry
+  const double* mass;     // T x nb or null
+  const double* inertia;  // T x nb x 9 (row-major 3 x 3, body frame) or null
+  const double* damp;     // T x nb x 6 (c_v, c_w per body: F = -c_v o v1, tau = -c_w o w1) or null
+  const int* rec;       // T x R non-decreasing 1-based storage indices
+  double* cs;           // T x 13 nb: the current CStates
+  int* cursor;          // T: records written so far (R: the trajectory has ended)
+  int* status;          // T: OR of the per-step statuses; 2 = a failed step ended the trajectory
+  double* out;          // T x R x 13 nb recorded CStates (NaN after a failed step)
+};
 void launch_project(const ProjArgs& a, hipStream_t s);
 void launch_vi_step(const ViArgs& a, hipStream_t s);
+void launch_simulate(const SimArgs& a, hipStream_t s);
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s);

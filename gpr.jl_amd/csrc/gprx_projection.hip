@@ -546,23 +546,45 @@ __device__ void subjoint_pose_jac(const PState& P, const SubJoint& J, int n6, do
     }
   }
 }
+// Where the step reads its bodies.  MechBodies: the launch-wide mechanism's nominal masses and
+// inertias and no external force (k_vi_step, the MeanDynamics rollouts).  TrajBodies: one
+// trajectory's own, in LDS, and the external force of the current step, ext[6 b + c] = F_c (world
+// frame, c < 3) or 2 tau_(c-3) (body frame) (k_simulate).
+struct MechBodies {
+  const MechDev& M;
+  static constexpr bool forced = false, stall_stop = false;
+  __device__ __forceinline__ double m(int b) const { return M.m[b]; }
+  __device__ __forceinline__ double J(int b, int i, int k) const { return M.J[b][i][k]; }
+  __device__ __forceinline__ double ext(int) const { return 0.0; }
+};
+struct TrajBodies {
+  const double* mm;            // nb
+  const double (*JJ)[3][3];    // nb
+  const double* fx;            // 6 nb
+  static constexpr bool forced = true, stall_stop = true;
+  __device__ __forceinline__ double m(int b) const { return mm[b]; }
+  __device__ __forceinline__ double J(int b, int i, int k) const { return JJ[b][i][k]; }
+  __device__ __forceinline__ double ext(int j) const { return fx[j]; }
+};
 // the dynamics rows of the residual, lane j < n6: body b = j / 6
-__device__ __forceinline__ double vi_dyn_row(const PState& P, const MechDev& M, const double (*mom1)[3], const double* G,
+template <class Bodies>
+__device__ __forceinline__ double vi_dyn_row(const PState& P, const Bodies& B, const double (*mom1)[3], const double* G,
                                              int n6, int nd, double dt, double grav, int j) {
   const int b = j / 6, c = j - 6 * b;
   const double* v2 = P.s + 6 * b;
   const double* w2 = v2 + 3;
   double d;
   if (c < 3) {
-    d = M.m[b] * ((v2[c] - P.vc[b][c]) / dt + (c == 2 ? grav : 0.0));
+    d = B.m(b) * ((v2[c] - P.vc[b][c]) / dt + (c == 2 ? grav : 0.0));
   } else {
     const int k = c - 3;
     double Jw[3];
-    for (int i = 0; i < 3; ++i) Jw[i] = M.J[b][i][0] * w2[0] + M.J[b][i][1] * w2[1] + M.J[b][i][2] * w2[2];
+    for (int i = 0; i < 3; ++i) Jw[i] = B.J(b, i, 0) * w2[0] + B.J(b, i, 1) * w2[1] + B.J(b, i, 2) * w2[2];
     const double sq2 = sqrt(4.0 / (dt * dt) - (w2[0] * w2[0] + w2[1] * w2[1] + w2[2] * w2[2]));
     const double cr = k == 0 ? w2[1] * Jw[2] - w2[2] * Jw[1] : (k == 1 ? w2[2] * Jw[0] - w2[0] * Jw[2] : w2[0] * Jw[1] - w2[1] * Jw[0]);
     d = (sq2 * Jw[k] + cr) - mom1[b][k];
   }
+  if constexpr (Bodies::forced) d = d - B.ext(j);  // - F, - 2 tau
   double t = 0.0;
   for (int r = 0; r < nd; ++r) t += G[(size_t)r * n6 + j] * P.s[n6 + r];
   return d - t;
@@ -587,9 +609,11 @@ __device__ __forceinline__ double skew_at(const double* v, int i, int j) {
 // the norms run redundantly on every wave from the same LDS values, so every wave takes the same
 // branch without a broadcast.  Each element sees the same operations in the same order for any
 // NW (k_vi_step's NW = 1 included).  Ends with a barrier: the caller may reuse the dynamic LDS.
-template <int NW>
-__device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double dt, double reg, double eps, double grav,
-                         int iters, int& it) {
+// B: the bodies' masses and inertias and the external force (MechBodies / TrajBodies above), constant
+// during the solve, so the Newton matrix has no term of it; TrajBodies also ends a stagnated solve.
+template <int NW, class Bodies>
+__device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, const Bodies& B, double dt, double reg, double eps,
+                         double grav, int iters, int& it) {
   constexpr int NT = 64 * NW;
   const int tid = threadIdx.x & (NT - 1), l = tid & 63;
   const bool w0 = tid < 64;
@@ -599,7 +623,7 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
   if (w0 && l < nb) {  // (sq1 I - [w1 x]) J w1; setsolution!: (v2, w2) start at the current velocities
     const double* w1 = P.wc[l];
     double Jw[3];
-    for (int i = 0; i < 3; ++i) Jw[i] = M.J[l][i][0] * w1[0] + M.J[l][i][1] * w1[1] + M.J[l][i][2] * w1[2];
+    for (int i = 0; i < 3; ++i) Jw[i] = B.J(l, i, 0) * w1[0] + B.J(l, i, 1) * w1[1] + B.J(l, i, 2) * w1[2];
     const double sq1 = sqrt(4.0 / (dt * dt) - (w1[0] * w1[0] + w1[1] * w1[1] + w1[2] * w1[2]));
     const double cr[3] = {w1[1] * Jw[2] - w1[2] * Jw[1], w1[2] * Jw[0] - w1[0] * Jw[2], w1[0] * Jw[1] - w1[1] * Jw[0]};
     for (int i = 0; i < 3; ++i) {
@@ -615,6 +639,7 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
   pj_sync<NW>();
   int status = 1;
   it = 0;
+  [[maybe_unused]] double nds_prev = INFINITY;
   for (int k = 1; k <= iters; ++k) {
     // ---- the Newton matrix and the residual at the current solution
     for (int i = tid; i < n * ldf; i += NT) A[i] = 0.0;
@@ -626,13 +651,13 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
         const int e = l - M.nsub, b = e / 9, i = (e - 9 * b) / 3, kk = e - 9 * b - 3 * i;
         const double* w2 = P.s + 6 * b + 3;
         double Jw[3];
-        for (int q = 0; q < 3; ++q) Jw[q] = M.J[b][q][0] * w2[0] + M.J[b][q][1] * w2[1] + M.J[b][q][2] * w2[2];
+        for (int q = 0; q < 3; ++q) Jw[q] = B.J(b, q, 0) * w2[0] + B.J(b, q, 1) * w2[1] + B.J(b, q, 2) * w2[2];
         const double sq2 = sqrt(4.0 / (dt * dt) - (w2[0] * w2[0] + w2[1] * w2[1] + w2[2] * w2[2]));
-        const double swJ = skew_at(w2, i, 0) * M.J[b][0][kk] + skew_at(w2, i, 1) * M.J[b][1][kk] + skew_at(w2, i, 2) * M.J[b][2][kk];
-        A[(6 * b + 3 + i) * ldf + 6 * b + 3 + kk] = ((sq2 * M.J[b][i][kk] + swJ) - skew_at(Jw, i, kk)) - sel3(Jw, i) * w2[kk] / sq2;
+        const double swJ = skew_at(w2, i, 0) * B.J(b, 0, kk) + skew_at(w2, i, 1) * B.J(b, 1, kk) + skew_at(w2, i, 2) * B.J(b, 2, kk);
+        A[(6 * b + 3 + i) * ldf + 6 * b + 3 + kk] = ((sq2 * B.J(b, i, kk) + swJ) - skew_at(Jw, i, kk)) - sel3(Jw, i) * w2[kk] / sq2;
       } else if (l < M.nsub + 12 * nb) {
         const int e = l - M.nsub - 9 * nb, b = e / 3, c = e - 3 * b;
-        A[(6 * b + c) * ldf + 6 * b + c] = M.m[b] / dt;
+        A[(6 * b + c) * ldf + 6 * b + c] = B.m(b) / dt;
       }
     }
     for (int e = tid; e < n6 * nd; e += NT) {  // -Gpos^T (upper right), -reg I (lower right)
@@ -641,7 +666,7 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
     }
     if (w0 && l < nd && reg != 0.0) A[(n6 + l) * ldf + n6 + l] = -reg;
     pj_sync<NW>();
-    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, grav, l);
+    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, B, mom1, G, n6, nd, dt, grav, l);
     pj_sync<NW>();
     // a system that is not finite (|w| beyond 2/dt: the reference's sqrt throws a DomainError) or is
     // singular (SingularException) fails the state.  Every wave scans the whole matrix.
@@ -665,13 +690,23 @@ __device__ int vi_newton(PState& P, double (*mom1)[3], const MechDev& M, double 
     // ---- convergence: |f(s_new)| and |ds|
     if (w0 && l < M.nsub) subjoint(P, M.sub[l], n6, ldf, dt, true, false, false);
     pj_sync<NW>();
-    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, M, mom1, G, n6, nd, dt, grav, l);
+    if (w0 && l < n6) P.f[l] = vi_dyn_row(P, B, mom1, G, n6, nd, dt, grav, l);
     pj_sync<NW>();
     const double fv = l < n ? P.f[l] : 0.0, dv = l < n ? P.ds[l] : 0.0;
     const double nf = sqrt(wave_sum(fv * fv)), nds = sqrt(wave_sum(dv * dv));
     if (nf < eps && nds < eps) {
       status = 0;
       break;
+    }
+    if constexpr (Bodies::stall_stop) {
+      // Stagnation at the rounding floor: the residual and the twist's step are below eps and |ds|, which
+      // the multipliers' step dominates, no longer falls.  At a small dt the multipliers' floor,
+      // (m / dt) (1e-16 / dt), lies above eps and newton!'s test can never hold; further iterations only
+      // move the last bits.  The step ends with status 1 (newton!'s test not met) and is used as it is.
+      const double tv = l < n6 ? P.ds[l] : 0.0;
+      const double ntw = sqrt(wave_sum(tv * tv));
+      if (nf < eps && ntw < eps && nds >= nds_prev) break;
+      nds_prev = nds;
     }
   }
   pj_sync<NW>();
@@ -716,7 +751,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   const int nb = a.mech.nb;
   set_states(P, a.cs + (size_t)t * 13 * nb, nb, a.dt, l);
   int it;
-  const int status = vi_newton<1>(P, mom1, a.mech, a.dt, a.reg, a.eps, a.grav, a.iters, it);
+  const int status = vi_newton<1>(P, mom1, a.mech, MechBodies{a.mech}, a.dt, a.reg, a.eps, a.grav, a.iters, it);
   double* o = a.out + (size_t)t * 13 * nb;
   for (int i = l; i < 13 * nb; i += 64) {
     const int b = i / 13, k = i - 13 * b;
@@ -729,6 +764,81 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   if (l == 0) {
     a.iters_out[t] = it;
     a.status[t] = status;
+  }
+}
+
+// ---- simulate!: many variational-integrator steps of T independent trajectories, one wave each ----
+// The datasets' simulations (examples/utils/data/simulations.jl; examples/parallel/dataframes.jl reads
+// their storage): per step control! (viscous friction from the current velocities: F = -c_v o v1 in
+// the world frame, tau = -c_w o w1 in the body frame), newton!, and the next CState [x2, q2, v2, w2]
+// -- what k_vi_step writes, taken up by set_states exactly as a host loop over k_vi_step hands it
+// back, so S steps here equal S launches of one step bit for bit.  The bodies are the trajectory's
+// own (mass / inertia: the datasets' dm, dJ), read once into LDS.  The trajectory is not stored: rec
+// lists the storage indices wanted (1 = the start, j = after j - 1 steps: saveToStorage! before
+// each step), and the trajectory ends after its last one.  A failed step (status 2) ends it with
+// NaN in the remaining records; one that only runs out of iterations is used as it is (the
+// MeanDynamics rollouts' contract).  One launch takes steps [step0, step0 + nsteps); cs, cursor and
+// status carry the trajectory to the next launch.  Every loop is bounded by nsteps, R or iters.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_simulate(SimArgs a) {
+  __shared__ PState P;
+  __shared__ double mom1[PJ_MAXB][3];
+  __shared__ double cs[13 * PJ_MAXB];
+  __shared__ double bm[PJ_MAXB], bJ[PJ_MAXB][3][3], bc[6 * PJ_MAXB], ext[6 * PJ_MAXB];
+  const int t = blockIdx.x, l = threadIdx.x;
+  const int nb = a.mech.nb, n6 = 6 * nb, d = 13 * nb, R = a.R;
+  int r = a.cursor[t];
+  if (r >= R) return;  // the trajectory has ended (the same on every lane)
+  const int* rec = a.rec + (size_t)t * R;
+  double* gcs = a.cs + (size_t)t * d;
+  double* out = a.out + (size_t)t * R * d;
+  for (int i = l; i < d; i += 64) cs[i] = gcs[i];
+  if (l < nb) bm[l] = a.mass ? a.mass[(size_t)t * nb + l] : a.mech.m[l];
+  for (int i = l; i < 9 * nb; i += 64) {
+    const int b = i / 9, e = i - 9 * b;
+    bJ[b][e / 3][e % 3] = a.inertia ? a.inertia[(size_t)t * 9 * nb + i] : a.mech.J[b][e / 3][e % 3];
+  }
+  if (l < n6) bc[l] = a.damp ? a.damp[(size_t)t * n6 + l] : 0.0;
+  pj_sync<1>();
+  const TrajBodies B{bm, bJ, ext};
+  const int kend = a.step0 + a.nsteps;
+  int st = 0, next = rec[r];
+  bool failed = false;
+  for (int k = a.step0;; ++k) {  // cs is the state of storage index k + 1
+    while (r < R && next <= k + 1) {
+      for (int i = l; i < d; i += 64) out[(size_t)r * d + i] = cs[i];
+      ++r;
+      if (r < R) next = rec[r];
+    }
+    if (r >= R || k >= kend) break;
+    set_states(P, cs, nb, a.dt, l);
+    pj_sync<1>();
+    if (l < n6) {  // control!: F = -c_v o v1, and 2 tau = -2 c_w o w1 as the rotational row takes it
+      const int b = l / 6, c = l - 6 * b;
+      ext[l] = c < 3 ? -(bc[l] * P.vc[b][c]) : 2.0 * -(bc[l] * P.wc[b][c - 3]);
+    }
+    pj_sync<1>();
+    int it;
+    const int s = vi_newton<1>(P, mom1, a.mech, B, a.dt, a.reg, a.eps, a.grav, a.iters, it);
+    if (s == 2) {  // the same on every lane
+      failed = true;
+      break;
+    }
+    st |= s;
+    for (int i = l; i < d; i += 64) {  // the solution CState, as k_vi_step writes it
+      const int b = i / 13, c = i - 13 * b;
+      cs[i] = c < 3 ? P.xk[b][c] : (c < 7 ? P.qk[b][c - 3] : P.s[6 * b + (c - 7)]);
+    }
+    pj_sync<1>();
+  }
+  if (failed) {
+    for (; r < R; ++r)
+      for (int i = l; i < d; i += 64) out[(size_t)r * d + i] = NAN;
+  } else {
+    for (int i = l; i < d; i += 64) gcs[i] = cs[i];
+  }
+  if (l == 0) {
+    a.cursor[t] = r;
+    a.status[t] = failed ? 2 : (a.status[t] | st);
   }
 }
 
@@ -812,7 +922,7 @@ void k_rollout_max(Args a) {
       if (w == 0) set_states(*Q, obs, nb, a.dt, l);
       __syncthreads();
       int vit;
-      const int vs = vi_newton<NW>(*Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
+      const int vs = vi_newton<NW>(*Q, mom1, a.mech, MechBodies{a.mech}, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
       vis |= vs;
       if (vs == 2) {  // the same on every wave
         if (tid == 0) P.status = 2;
@@ -1042,7 +1152,7 @@ __global__ __launch_bounds__(256) void k_rollout(Args a) {
       if (tid < 64) set_states(Q, cs, nb, a.dt, tid);
       __syncthreads();
       int vit;
-      const int vs = vi_newton<NW>(Q, mom1, a.mech, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
+      const int vs = vi_newton<NW>(Q, mom1, a.mech, MechBodies{a.mech}, a.dt, a.vi.reg, a.vi.eps, a.vi.grav, a.vi.iters, vit);
       vis |= vs;
       if (vs == 2) {  // the same on every wave
         failed = true;
@@ -1097,6 +1207,9 @@ void launch_project(const ProjArgs& a, hipStream_t s) {
 }
 void launch_vi_step(const ViArgs& a, hipStream_t s) {
   if (a.T > 0) hipLaunchKernelGGL(k_vi_step, dim3(a.T), dim3(64), vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s, a);
+}
+void launch_simulate(const SimArgs& a, hipStream_t s) {
+  if (a.T > 0) hipLaunchKernelGGL(k_simulate, dim3(a.T), dim3(64), vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s, a);
 }
 void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s) {
   if (a.T <= 0) return;

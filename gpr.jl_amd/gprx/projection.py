@@ -86,6 +86,49 @@ def vi_step(mech: str, cstates, regularizer: float | None = None, newton_iter: i
     return out, it, st
 
 
+def simulate(mech: str, start, steps: int, rec, mass=None, inertia=None, damp=None, regularizer: float | None = None,
+             newton_iter: int = 100, eps: float = 1e-10, dt: float = DT, steps_per_launch: int = 0,
+             ctx: Context | None = None):
+    """simulate!(mechanism, steps dt, control!, record = true) of the reference's datasets
+    (examples/utils/data/simulations.jl) for T trajectories, every step on the device (gprx_simulate,
+    k_simulate: one wave per trajectory).  start (T, 13 nb) CStates; rec (T, R) or (R,) non-decreasing
+    1-based storage indices in [1, steps + 1] (1 = the start, j = after j - 1 steps); mass (T, nb),
+    inertia (T, nb, 3, 3), damp (T, nb, 6) = (c_v, c_w) per body, or their single-trajectory shapes for
+    all; None: the nominal bodies / no friction (gprx.vi.vi_step documents the equations).  Returns
+    (records (T, R, 13 nb), NaN after a failed step; status (T,): OR of the per-step statuses, 2 =
+    a failed step ended the trajectory).  A solve that stagnates at the rounding floor ends with status 1
+    (gprx.vi.vi_step's stall_stop)."""
+    from . import vi
+
+    if mech not in MECH:
+        raise ValueError(f"Experiment {mech} not supported!")
+    nb = NBODIES[mech]
+    S = np.ascontiguousarray(np.atleast_2d(start), dtype=np.float64)
+    T = S.shape[0]
+    if S.shape != (T, 13 * nb):
+        raise ValueError(f"start must be (T, {13 * nb})")
+    rc = np.asarray(rec, dtype=np.int32)
+    rc = np.ascontiguousarray(np.broadcast_to(rc, (T, rc.shape[-1])) if rc.ndim == 1 else rc)
+    if rc.ndim != 2 or rc.shape[0] != T or rc.shape[1] < 1:
+        raise ValueError("rec must be (T, R) or (R,), R >= 1")
+    R = rc.shape[1]
+
+    def per_traj(a, shape):
+        if a is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (T,) + shape))
+
+    m, J, c = per_traj(mass, (nb,)), per_traj(inertia, (nb, 3, 3)), per_traj(damp, (nb, 6))
+    reg = vi.REGULARIZER[mech] if regularizer is None else float(regularizer)
+    ctx = ctx or _default_ctx()
+    out = np.empty((T, R, 13 * nb))
+    st = np.empty(T, dtype=np.int32)
+    L.check(L.lib.gprx_simulate(ctx.h, MECH[mech], float(dt), int(steps), T, L.dptr(S), L.dptr(m), L.dptr(J), L.dptr(c), reg,
+                                int(newton_iter), float(eps), R, L.iptr(rc), int(steps_per_launch), L.dptr(out), L.iptr(st)),
+            ctx.h)
+    return out, st
+
+
 def predictdynamics(mech: str, groups, start, steps: int, vw_indices, regularizer: float | None = None,
                     traj_group=None, dt: float = DT, ctx: Context | None = None):
     """predictdynamics(mechanism, gps, startobservation, steps, getvw; regularizer) for T

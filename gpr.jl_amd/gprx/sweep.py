@@ -33,7 +33,10 @@ Variants (all of noise.jl:72-85):
              GP means of a rollout step come from one batched device predict, the projection
              from the device
 Data are the synthetic generator's (gprx.data; the .jls datasets are absent), seeded per
-(mechanism, trial) as 1000 * config_id + trial (data.trial_seed).
+(mechanism, trial) as 1000 * config_id + trial (data.trial_seed).  Opt-in (run_group(dataset=...),
+--dataset DIR): trials from datasets simulated as the reference simulates its own (gprx.simdata;
+the vi, max and md_max variants), the truth their noise-free sfuture rows -- the physically
+meaningful numbers; the synthetic generator's P2, CP and FB targets advance at constant rates.
 """
 from __future__ import annotations
 
@@ -60,6 +63,7 @@ ETYPE = {"max": "noisy", "min": "noisy", "min_sin": "noisysin", "md_max": "noisy
 # in the reference tree: its only cross-check is the repo's own action-based oracle/vi_oracle.py
 # (same modelling assumptions), so those entries are not reference-equivalent numbers.
 MD_ROLLOUTS = ("stepwise", "device")  # run_group's md_rollout
+DATASET_VARIANTS = ("vi", "max", "md_max")  # what run(dataset=...) / --dataset can build trials for
 PARITY = {"max": "gp: oracle-pinned; physics: projectv! restated (unpinned vs ConstrainedDynamics)",
           "min": "gp: oracle-pinned", "min_sin": "gp: oracle-pinned",
           "vi": "unpinned: gprx.vi restates ConstrainedDynamics 0.7.4 newton! (absent from the reference tree)",
@@ -74,17 +78,40 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
-def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, ctx=None) -> list[dict]:
-    """The trials' GP inputs, built on the rank that owns them (MeanDynamics means on ctx's device)."""
+def _dataset_of(dataset, trial: int) -> dict:
+    """Trial `trial`'s dataset: the reference's trial id picks df[id] (P2noise.jl:12)."""
+    return dataset if isinstance(dataset, dict) else dataset[trial % len(dataset)]
+
+
+def _truth(mech: str, trial: dict, testsamples: int, simsteps: int) -> np.ndarray:
+    """xtest_future_true (M, d): a dataset trial's sfuture rows, else the synthetic generator's."""
+    if "truth" in trial:
+        return trial["truth"]
+    return data.test_truth(mech, testsamples, trial["seed"], simsteps)["X"].T
+
+
+def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, ctx=None, dataset=None) -> list[dict]:
+    """The trials' GP inputs, built on the rank that owns them (MeanDynamics means on ctx's device).
+    dataset: a gprx.simdata dataset (or a list, one per trial id modulo its length) instead of the
+    synthetic generator; maximal coordinates only."""
     out = []
     md = variant.startswith("md_")
     base = variant[3:] if md else variant
+    if dataset is not None and base != "max":
+        raise ValueError(f"dataset trials are built for the maximal-coordinate variants, not {variant!r}")
     for t in trial_ids:
         seed = data.trial_seed(mech, t)
         if base == "max":
-            tr = data.make_trial(mech, N, testsamples, seed=seed)
+            if dataset is not None:
+                from . import simdata
+
+                tr = simdata.trial_from_dataset(mech, _dataset_of(dataset, t), N, testsamples, seed=seed)
+            else:
+                tr = data.make_trial(mech, N, testsamples, seed=seed)
             th = data.theta0(mech, N, "MAX")
             d = dict(X=tr["X"], Y=tr["Y"], Xs=tr["Xs"], theta=np.tile(th, (tr["Y"].shape[0], 1)), trial=t, seed=seed)
+            if "truth" in tr:
+                d["truth"] = tr["truth"]
             if md:  # MeanDynamics prior mean, once per training set (gprx.mdynamics)
                 d["mu"] = mdynamics.mean_max(mech, tr["X"], ctx=ctx)
         else:
@@ -110,7 +137,7 @@ def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, c
 
 def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
               max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
-              trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise") -> dict:
+              trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise", dataset=None) -> dict:
     """One (mechanism, N, variant) group for this rank's trials: device optimise of every GP,
     then the variant's evaluation.  Returns per-trial arrays (n_local, ...) and timings.
     trials: prebuilt local_trials-shaped inputs (the hyper-parameter search's), else noise.jl's.
@@ -119,11 +146,12 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     bit-identical results; keep=True (the batch returned for inspection) needs one batch.
     md_rollout: how the md_* variants roll out -- "stepwise" (a host loop of three device calls per
     step, gprx.mdynamics.rollout_max / rollout_min) or "device" (every step in one launch,
-    gprx.mdynamics.rollout_max_device / rollout_min_device)."""
+    gprx.mdynamics.rollout_max_device / rollout_min_device).
+    dataset: take the trials from simulated datasets (local_trials) and the truth from their sfuture."""
     if md_rollout not in MD_ROLLOUTS:
         raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")
     if trials is None:
-        trials = local_trials(mech, N, variant, trial_ids, testsamples, ctx)
+        trials = local_trials(mech, N, variant, trial_ids, testsamples, ctx, dataset)
     n = len(trials)
     if n == 0:
         return {}
@@ -181,7 +209,7 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
                 sl = slice(k * testsamples, (k + 1) * testsamples)
                 if np.any(st[sl] != 0):  # a singular projection throws in the reference: trial dropped
                     continue
-                truth = data.test_truth(mech, testsamples, trials[i]["seed"], simsteps)["X"].T
+                truth = _truth(mech, trials[i], testsamples, simsteps)
                 err[i] = data.position_mse(truth, fin[sl])
                 perr[i] = float(np.mean(pe[sl]))  # projectionerror / length(xtest_old) (P2noise.jl:51)
                 failed[i] = False
@@ -195,7 +223,7 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
             for k, i in enumerate(good):
                 if np.any(st[k] != 0) or np.isnan(fin[k]).any():  # singular projection / failed physics mean
                     continue
-                truth = data.test_truth(mech, testsamples, trials[i]["seed"], simsteps)["X"].T
+                truth = _truth(mech, trials[i], testsamples, simsteps)
                 err[i] = data.position_mse(truth, fin[k])
                 perr[i] = float(np.mean(pe[k]))
                 failed[i] = False
@@ -208,7 +236,7 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
             for k, i in enumerate(good):
                 if np.isnan(fin[k]).any():  # a failed physics mean (vi_step status 2) throws in the reference
                     continue
-                truth = data.test_truth(mech, testsamples, trials[i]["seed"], simsteps)["X"].T
+                truth = _truth(mech, trials[i], testsamples, simsteps)
                 err[i] = data.position_mse(truth, fin[k])
                 failed[i] = False
     else:
@@ -223,7 +251,7 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
             for k, i in enumerate(good):
                 f = fin[k * testsamples:(k + 1) * testsamples]
                 pred = np.stack([final_cstate(mech, row[0::2]) for row in f])
-                truth = data.test_truth(mech, testsamples, trials[i]["seed"], simsteps)["X"].T
+                truth = _truth(mech, trials[i], testsamples, simsteps)
                 err[i] = data.position_mse(truth, pred)
                 failed[i] = False
     t_eval = time.perf_counter() - t1
@@ -232,11 +260,13 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
                 slots=n * G, batches=1)
 
 
-def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int = 20, ctx=None) -> dict:
+def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int = 20, ctx=None, dataset=None,
+                    noise: bool = True) -> dict:
     """The pure variational-integrator baseline (noise.jl:72-75, examples/baseline.jl:3-16
     experimentVarInt): every noisy test start simulated for simsteps + 1 physics steps
     (gprx.mdynamics.simulate, the device step), error = simulationerror against the noise-free
-    truth.  No GP."""
+    truth.  No GP.  dataset: the test starts and the truth from simulated datasets (noise=False: the
+    stored starts, which the baseline then follows exactly)."""
 
     n = len(trial_ids)
     err = np.full(n, math.inf)
@@ -246,7 +276,15 @@ def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int 
     seeds = [data.trial_seed(mech, t) for t in trial_ids]
     # every test start of every local trial in one vectorised simulation (the states are
     # independent: each one's Newton iterates are those of a per-trial call)
-    start = np.concatenate([data.make_trial(mech, 2, testsamples, seed=sd)["Xs"].T for sd in seeds])
+    if dataset is not None:
+        from . import simdata
+
+        trs = [simdata.trial_from_dataset(mech, _dataset_of(dataset, t), 0, testsamples, seed=sd, noise=noise)
+               for t, sd in zip(trial_ids, seeds)]
+        start = np.concatenate([tr["Xs"].T for tr in trs])
+    else:
+        trs = [dict(seed=sd) for sd in seeds]
+        start = np.concatenate([data.make_trial(mech, 2, testsamples, seed=sd)["Xs"].T for sd in seeds])
     fin, st = mdynamics.simulate(mech, start, simsteps, ctx=ctx)
     for k, sd in enumerate(seeds):
         sl = slice(k * testsamples, (k + 1) * testsamples)
@@ -255,15 +293,17 @@ def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int 
         if np.any(st[sl] & 2):
             failed[k] = True
             continue
-        err[k] = data.position_mse(data.test_truth(mech, testsamples, sd, simsteps)["X"].T, fin[sl])
+        err[k] = data.position_mse(_truth(mech, trs[k], testsamples, simsteps), fin[sl])
     return dict(kstep_mse=err, failed=failed)
 
 
 def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
         max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None,
-        md_rollout: str = "stepwise") -> dict:
+        md_rollout: str = "stepwise", dataset=None) -> dict:
     """The sweep.  Every rank runs its trials of every group; rank 0 returns the gathered
-    checkpoint dict (other ranks None).  Without an initialised process group: one rank."""
+    checkpoint dict (other ranks None).  Without an initialised process group: one rank.
+    dataset: a directory of simulated datasets (gprx.simdata.load_datasets) instead of the synthetic
+    generator."""
     from .batch import Context
 
     dist = _dist()
@@ -275,10 +315,19 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
     mine = shard.shard_trials(n_trials, rank, world)
     results: dict = {}
     timing: dict = {}
+    if dataset is not None:  # refused before any work: dataset trials exist in maximal coordinates only
+        bad = [v for v in variants if v not in DATASET_VARIANTS]
+        if bad:
+            raise ValueError(f"--dataset runs the variants {DATASET_VARIANTS}, not {bad}: pass --variants")
     for mech in mechs:
+        dsets = None
+        if dataset is not None:
+            from . import simdata
+
+            dsets = simdata.load_datasets(dataset, mech)
         if "vi" in variants:  # the pure variational-integrator baseline (noise.jl:72-75, idmod "VI")
             t0 = time.perf_counter()
-            r = run_vi_baseline(mech, mine, testsamples, simsteps, ctx)
+            r = run_vi_baseline(mech, mine, testsamples, simsteps, ctx, dataset=dsets)
             loc = {"kstep_mse": r["kstep_mse"].reshape(-1, 1), "failed": r["failed"].astype(np.float64).reshape(-1, 1),
                    "t": np.full((len(mine), 1), time.perf_counter() - t0)}
             g = shard.gather_results(loc, n_trials, lambda q: shard.shard_trials(n_trials, q, world), 0,
@@ -297,7 +346,8 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
             for var in variants:
                 if var == "vi":
                     continue
-                r = run_group(mech, N, var, mine, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout=md_rollout)
+                r = run_group(mech, N, var, mine, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout=md_rollout,
+                              dataset=dsets)
                 local = {"kstep_mse": r.get("kstep_mse", np.zeros(0)), "perr": r.get("projectionerror", np.zeros(0)),
                          "failed": r.get("failed", np.zeros(0, dtype=bool)).astype(np.float64),
                          "ok": np.all(r["status"] == 0, axis=1).astype(np.float64) if r else np.zeros(0),
@@ -328,8 +378,11 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
                             f"{timing[f'{key}/{var}']['seconds_max_rank']:.3f} s")
     if rank != 0:
         return None
-    return {"results": results, "timing": timing, "world": world, "n_trials": n_trials, "max_evals": max_evals,
-            "time_limit": time_limit, "testsamples": testsamples, "simsteps": simsteps}
+    out = {"results": results, "timing": timing, "world": world, "n_trials": n_trials, "max_evals": max_evals,
+           "time_limit": time_limit, "testsamples": testsamples, "simsteps": simsteps}
+    if dataset is not None:
+        out["data"] = f"simulated datasets: {dataset}"
+    return out
 
 
 def main(argv=None):
@@ -344,6 +397,9 @@ def main(argv=None):
     ap.add_argument("--time-limit", type=float, default=float("nan"), help="seconds per group call (NaN: none)")
     ap.add_argument("--md-rollout", choices=MD_ROLLOUTS, default="stepwise",
                     help="the md_* variants' rollout: a host loop of device calls per step, or one device launch")
+    ap.add_argument("--dataset", default=None,
+                    help="directory of simulated datasets (gprx.simdata.write_dataset: DIR/<mech>[/<k>]) instead of "
+                         "the synthetic generator; the vi, max and md_max variants")
     ap.add_argument("--out", default="gpurun_out/sweep_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -361,7 +417,7 @@ def main(argv=None):
     res = run([m for m in a.mechs.split(",") if m], [int(s) for s in a.sizes.split(",") if s],
               [v for v in a.variants.split(",") if v], a.trials, a.testsamples, a.simsteps,
               a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True), md_rollout=a.md_rollout)
+              log=lambda s: print(s, flush=True), md_rollout=a.md_rollout, dataset=a.dataset)
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

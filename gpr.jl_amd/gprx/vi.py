@@ -227,11 +227,58 @@ def _dphi_dw(q2, q3, w, dt=DT):
 
 
 # ---- the step -----------------------------------------------------------------------------------
-def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_iter: int = 100):
+def body_params(mech_name: str, dm=None, dJ=None):
+    """The bodies of one mechanism with the datasets' perturbations, in the reference's order of
+    operations (simulations.jl:9,43 / :55,96-97 / :113,151 / :165,204): m_b = 1.0 dm_b and
+    J_b = I (((1/12) m_b) l^2) dJ_b, l = 1 (P1, P2, FB) or 0.5 (the CP pole, whose dJ is a scalar:
+    "only change inertia of the pendulum", datasets.jl:55); the CP cart keeps Box(0.2, 0.3, 0.1, m)'s
+    inertia.  dm, dJ: per body (scalars for P1; dJ a scalar for CP); None = 1.  Returns m (nb,),
+    J (nb, 3, 3)."""
+    nb = MECHANISMS[mech_name]["nb"]
+    dm = np.ones(nb) if dm is None else np.broadcast_to(np.asarray(dm, dtype=np.float64), (nb,))
+    m = 1.0 * dm
+    if mech_name == "CP":
+        dj = 1.0 if dJ is None else float(np.asarray(dJ, dtype=np.float64).reshape(-1)[-1])
+        return m, np.stack([_box_inertia(m[0], 0.2, 0.3, 0.1), np.eye(3) * (1 / 12 * m[1] * 0.5 ** 2 * dj)])
+    dj = np.ones(nb) if dJ is None else np.broadcast_to(np.asarray(dJ, dtype=np.float64), (nb,))
+    return m, np.stack([np.eye(3) * (1 / 12 * m[b] * 1.0 ** 2 * dj[b]) for b in range(nb)])
+
+
+def friction_damp(mech_name: str, friction=None):
+    """The reference's control! (simulations.jl:29-33, 80-85, 134-139, 191-193) as the per-body
+    6-vector damp = (c_v, c_w), F = -c_v o v1, tau = -c_w o w1: body i's w_x <- friction[i] (P1, P2,
+    FB); CP: the cart's v_y <- friction[1], the pole's w_x <- friction[2].  Returns (nb, 6)."""
+    nb = MECHANISMS[mech_name]["nb"]
+    c = np.zeros((nb, 6))
+    if friction is None:
+        return c
+    f = np.broadcast_to(np.asarray(friction, dtype=np.float64), (nb,))
+    for b in range(nb):
+        c[b, 1 if (mech_name == "CP" and b == 0) else 3] = f[b]
+    return c
+
+
+def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_iter: int = 100, m=None, J=None,
+            damp=None, regularizer=None, stall_stop: bool = False):
     """newton!(mechanism) after setstates!(mechanism, CState(x)) for T states.  cstates (T, 13 nb)
     -> the solution CStates (T, 13 nb) = [x2, q2, v2, w2] per body (CState(mechanism,
     usesolution=true), src/CState.jl:66-71), iterations (T,), status (T,) (1: not converged; 2:
-    failed, where the reference throws (DomainError / SingularException): its row is NaN)."""
+    failed, where the reference throws (DomainError / SingularException): its row is NaN).
+
+    m (nb,) or (T, nb), J (nb, 3, 3) or (T, nb, 3, 3): the bodies (None: the mechanism's nominal
+    ones).  damp (nb, 6) or (T, nb, 6) = (c_v, c_w) per body (None: none): the datasets' control!,
+    called before newton! with the current velocities, F = -c_v o v1 (world frame), tau = -c_w o w1
+    (body frame), constant during the solve; the dynamics rows become
+        m ((v2 - v1)/dt + g e_z) - F - Gpos_x^T lambda = 0
+        (sq2 I + [w2 x]) J w2 - (sq1 I - [w1 x]) J w1 - 2 tau - Gpos_phi^T lambda = 0
+    (the rotational row is 2 J w' as dt -> 0, so J w' = tau takes 2 tau; recalled from
+    ConstrainedDynamics 0.7.4's dynamics, `- state.Fk`, `- 2 tauk`: unpinned like the rest, the sign
+    and the factor are pinned physically by tests/test_sim_physics.py).
+
+    regularizer: the impulses' regularisation (None: REGULARIZER[mech_name]).  stall_stop (gprx_simulate's
+    rule): a solve whose residual and twist step are below eps while |ds|, which the multipliers' step
+    dominates, no longer falls has reached the rounding floor -- at a small dt the multipliers' floor
+    (m/dt)(1e-16/dt) lies above eps and newton!'s test can never hold; it ends there with status 1."""
     mech = MECHANISMS[mech_name]
     nb = mech["nb"]
     cs = np.atleast_2d(np.asarray(cstates, dtype=np.float64))
@@ -240,15 +287,30 @@ def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_
     x1, q1, v1, w1 = c[..., 0:3], c[..., 3:7], c[..., 7:10], c[..., 10:13]
     x2 = x1 + v1 * dt
     q2 = step_q(q1, w1, dt)
-    m = np.asarray(mech["m"])
-    J = np.stack(mech["J"])  # (nb, 3, 3)
+    m = np.asarray(mech["m"]) if m is None else np.asarray(m, dtype=np.float64)
+    J = np.stack(mech["J"]) if J is None else np.asarray(J, dtype=np.float64)  # (nb, 3, 3) or (T, nb, 3, 3)
+    if m.ndim == 1:
+        m_of = lambda a: m[None, :]  # noqa: E731
+    else:
+        m_of = lambda a: m[a]  # noqa: E731
+    if J.ndim == 3:
+        J_of = lambda a: J  # noqa: E731
+        Jmul = lambda a, w: np.einsum("bij,tbj->tbi", J, w)  # noqa: E731
+    else:
+        J_of = lambda a: J[a]  # noqa: E731
+        Jmul = lambda a, w: np.einsum("tbij,tbj->tbi", J[a], w)  # noqa: E731
+    ext = None  # (F, 2 tau) per body (T, nb, 6): control! at the current velocities
+    if damp is not None:
+        cd = np.broadcast_to(np.asarray(damp, dtype=np.float64), (T, nb, 6))
+        ext = np.concatenate([-(cd[..., 0:3] * v1), 2.0 * -(cd[..., 3:6] * w1)], axis=-1)
     n6 = 6 * nb
     Gpos = jac_phi(mech, x2, q2)  # (T, nd, n6): the k-pose force Jacobian (fixed during the solve)
     nd = Gpos.shape[1]
-    Jw1 = np.einsum("bij,tbj->tbi", J, w1)
+    Jw1 = Jmul(np.arange(T), w1)
     sq1 = np.sqrt(4.0 / dt ** 2 - np.sum(w1 * w1, axis=-1))
     mom1 = sq1[..., None] * Jw1 - np.cross(w1, Jw1)  # (sq1 I - [w1 x]) J w1
-    reg = REGULARIZER[mech_name]
+    reg = REGULARIZER[mech_name] if regularizer is None else float(regularizer)
+    nds_prev = np.full(T, np.inf)
     v2, w2 = v1.copy(), w1.copy()  # setsolution!: the solution starts at the current velocities
     lam = np.zeros((T, nd))
     it = np.zeros(T, dtype=np.int32)
@@ -257,11 +319,14 @@ def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_
 
     def residual(a, v2a, w2a, lama):
         """residual of the states a (index array) at (v2a, w2a, lama)"""
-        Jw2 = np.einsum("bij,tbj->tbi", J, w2a)
+        Jw2 = Jmul(a, w2a)
         sq2 = np.sqrt(4.0 / dt ** 2 - np.sum(w2a * w2a, axis=-1))
-        dT = m[None, :, None] * ((v2a - v1[a]) / dt + np.array([0.0, 0.0, GRAV]))
+        dT = m_of(a)[..., None] * ((v2a - v1[a]) / dt + np.array([0.0, 0.0, GRAV]))
         dR = sq2[..., None] * Jw2 + np.cross(w2a, Jw2) - mom1[a]
-        d = np.concatenate([dT, dR], axis=-1).reshape(len(a), n6) - np.einsum("tcj,tc->tj", Gpos[a], lama)
+        d = np.concatenate([dT, dR], axis=-1)
+        if ext is not None:
+            d = d - ext[a]
+        d = d.reshape(len(a), n6) - np.einsum("tcj,tc->tj", Gpos[a], lama)
         x3 = x2[a] + v2a * dt
         q3 = step_q(q2[a], w2a, dt)
         return np.concatenate([d, constraints(mech, x3, q3)], axis=1), Jw2, sq2, x3, q3
@@ -271,12 +336,14 @@ def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_
         na = len(a)
         f, Jw2, sq2, x3, q3 = residual(a, v2[a], w2[a], lam[a])
         F = np.zeros((na, n6 + nd, n6 + nd))
+        ma, Ja = m_of(a), J_of(a)
         for b in range(nb):
             o = 6 * b
-            F[:, o:o + 3, o:o + 3] = np.eye(3) * (m[b] / dt)
+            F[:, o:o + 3, o:o + 3] = np.eye(3) * (ma[:, b, None, None] / dt)
             # d/dw2 [(sq2 I + [w2 x]) J w2]
             wb = w2[a, b]
-            F[:, o + 3:o + 6, o + 3:o + 6] = (sq2[:, b, None, None] * J[b] + skew(wb) @ J[b] - skew(Jw2[:, b])
+            Jb = Ja[..., b, :, :]
+            F[:, o + 3:o + 6, o + 3:o + 6] = (sq2[:, b, None, None] * Jb + skew(wb) @ Jb - skew(Jw2[:, b])
                                               - Jw2[:, b, :, None] * wb[:, None, :] / sq2[:, b, None, None])
         F[:, :n6, n6:] = -np.swapaxes(Gpos[a], 1, 2)
         Gphi3 = jac_phi(mech, x3, q3)
@@ -314,8 +381,12 @@ def vi_step(mech_name: str, cstates, dt: float = DT, eps: float = 1e-10, newton_
         lam[a] -= ds[:, n6:]
         it[a] = k
         fn = np.linalg.norm(residual(a, v2[a], w2[a], lam[a])[0], axis=1)
-        conv = (fn < eps) & (np.linalg.norm(ds, axis=1) < eps)
+        nds = np.linalg.norm(ds, axis=1)
+        conv = (fn < eps) & (nds < eps)
         done[a[conv]] = True
+        if stall_stop:  # leaves the iteration, not converged by newton!'s test
+            conv = conv | ((fn < eps) & (np.linalg.norm(ds[:, :n6], axis=1) < eps) & (nds >= nds_prev[a]))
+            nds_prev[a] = nds
         a = a[~conv]
         if len(a) == 0:
             break
@@ -333,14 +404,15 @@ def mean_dynamics(mech_name: str, X, vw_indices, dt: float = DT):
     return sol[:, idx].T.copy()
 
 
-def simulate(mech_name: str, cstates, steps: int, dt: float = DT):
+def simulate(mech_name: str, cstates, steps: int, dt: float = DT, m=None, J=None, damp=None, **kw):
     """predictdynamics(mechanism, startobservation, steps) of the physics-only baseline
     (examples/utils/predictdynamics.jl:24-28 -> ConstrainedDynamics.simulate!(mechanism, 1:steps+1):
     newton! then updatestate!, steps + 1 times) for T start CStates: the final CStates (T, 13 nb)
-    and the states whose Newton solve did not converge at some step (T,)."""
+    and the states whose Newton solve did not converge at some step (T,).  m, J, damp: the bodies
+    and the friction of vi_step (the datasets' simulations)."""
     S = np.atleast_2d(np.asarray(cstates, dtype=np.float64))
     bad = np.zeros(S.shape[0], dtype=np.int32)
     for _ in range(steps + 1):
-        S, _, st = vi_step(mech_name, S, dt)  # the solution CState = CState(mechanism) after updatestate!
+        S, _, st = vi_step(mech_name, S, dt, m=m, J=J, damp=damp, **kw)  # the solution CState = CState(mechanism) after updatestate!
         bad |= st
     return S, bad
