@@ -1549,6 +1549,72 @@ int rollout_download(gprx_ctx* c, const RolloutIo& io, int T, double* final_stat
   return GPRX_OK;
 }
 
+// What the recorded entry points (gprx_rollout_*_rec) add to their one-launch counterparts: the
+// records wanted, the launch bound and where the records go.  A null RecReq is the one-launch call.
+struct RecReq {
+  int R;
+  const int* rec;
+  int steps_per_launch;
+  double* traj;
+};
+int rec_check(gprx_ctx* c, const std::string& fn, const RecReq& q, int steps, int T) {
+  if (q.R > 0 && (!q.rec || !q.traj)) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  for (int t = 0; t < T; ++t)
+    for (int r = 0; r < q.R; ++r) {
+      const int j = q.rec[(size_t)t * q.R + r];
+      if (j < 1 || j > steps + 1 || (r > 0 && j < q.rec[(size_t)t * q.R + r - 1]))
+        return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": rec must be non-decreasing per trajectory, in [1, steps + 1]");
+    }
+  return GPRX_OK;
+}
+// The device buffers of a recorded call follow the one-launch call's in its RolloutIo (the records
+// come back with the outputs); `row` doubles per record.
+constexpr size_t REC_EXTRAS = 5;
+void rec_extras(RolloutIo& io, const RecReq& q, size_t row) {
+  io.extra.push_back({q.traj, (size_t)q.R * row * sizeof(double), 0});
+  io.extra.push_back({nullptr, (size_t)q.R * sizeof(int), 0});                        // rec
+  io.extra.push_back({nullptr, sizeof(int), 0});                                      // cursor
+  io.extra.push_back({nullptr, (size_t)gprx::ROLLOUT_CARRY * sizeof(double), 0});     // carry
+  io.extra.push_back({nullptr, 2 * sizeof(int), 0});                                  // icarry
+}
+int rec_upload(gprx_ctx* c, const RolloutIo& io, const RecReq& q, int T, gprx::RolloutRec& rr) {
+  const size_t k = io.extra.size() - REC_EXTRAS;
+  rr.R = q.R;
+  rr.traj = q.R ? io.dev<double>(k) : nullptr;
+  rr.rec = q.R ? io.dev<int>(k + 1) : nullptr;
+  rr.cursor = io.dev<int>(k + 2);
+  rr.carry = io.dev<double>(k + 3);
+  rr.icarry = io.dev<int>(k + 4);
+  if (q.R) HIPCHK(c, hipMemcpyAsync(io.base + io.extra[k + 1].off, q.rec, (size_t)T * q.R * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return GPRX_OK;
+}
+// The default steps per launch of a recorded rollout keeps a launch near 0.2 s, as gprx_simulate's,
+// at the largest shapes the project rolls out: the four-bar, N = 512 (G = 12 maximal; usesin minimal).
+// A step of T trajectories takes lat + T traj seconds there -- the line through the two measurements on
+// an MI355X, T = 100 (the step chain's latency: the workgroups run side by side) and T = 3200 (several
+// rounds of resident workgroups) -- so the default falls with T (DESIGN.md section 4 has the figures).
+struct RecStepTime {
+  double lat, traj;  // seconds
+};
+constexpr RecStepTime REC_MAX{3.29e-3, 2.56e-6}, REC_MAX_MD{5.33e-3, 4.15e-6},  // 3.55 / 11.5 ms and 5.75 / 18.6 ms per step
+    REC_MIN{3.5e-6, 8.5e-9}, REC_MIN_MD{0.62e-3, 2.71e-6};                       // 0.0043 / 0.031 ms and 0.89 / 9.29 ms
+int rec_default_spl(const RecStepTime& s, int T) {
+  const double n = 0.2 / (s.lat + s.traj * T);
+  return n < 1.0 ? 1 : (n > 1e6 ? 1000000 : (int)n);
+}
+// steps [0, steps) in launches of at most spl steps (one launch when steps = 0: record 1 and the outputs)
+template <class Args, class Launch>
+int rec_launches(gprx_ctx* c, const char* stat, Args& a, int spl, double flops_step, double bytes_step, Launch launch) {
+  a.rr.step0 = 0;
+  do {
+    a.rr.nsteps = a.steps - a.rr.step0 < spl ? a.steps - a.rr.step0 : spl;
+    timed(c, c->stream, stat, flops_step * a.rr.nsteps, bytes_step * a.rr.nsteps, [&] { launch(a, c->dist_mode, c->stream); });
+    HIPCHK(c, hipGetLastError());
+    a.rr.step0 += a.rr.nsteps;
+  } while (a.rr.step0 < a.steps);
+  return GPRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1647,19 +1713,25 @@ int gprx_simulate(gprx_ctx* c, int mech, double dt, int steps, int T, const doub
 // gprx_rollout_min (vi_regularizer null: MeanZero GPs, k_rollout<., RolloutArgs>) and
 // gprx_rollout_min_md (predictdynamicsmin with MeanDynamics GPs, examples/utils/predictdynamics.jl:
 // 30-102 with src/mDynamics.jl:41-55: the physics mean per step, k_rollout<., RolloutMinMdArgs>): one
-// validation, scratch layout and launch
+// validation, scratch layout and launch.  With rq (gprx_rollout_min_rec, gprx_rollout_min_md_rec) the
+// same call keeps the records rq names and runs as launches of at most rq->steps_per_launch steps of
+// the recording instantiations, the records, cursor and carried state further entries of the scratch.
 static int rollout_min_call(gprx_ctx* c, const std::string& fn, const char* stat, int mech, int usesin, double dt, int steps,
                             const double* vi_regularizer, int ngroups, gprx_batch* const* batches, const int* slots, int T,
-                            const int* traj_group, const double* start, double* final_state, int* status, int* vi_status) {
+                            const int* traj_group, const double* start, double* final_state, int* status, int* vi_status,
+                            const RecReq* rq = nullptr) {
   if (!c) return GPRX_INVALID_ARGUMENT;
-  gprx::RolloutMinMdArgs a{};
+  gprx::RolloutMinMdRecArgs a{};  // every form's arguments: each launcher takes the part it knows
   // The MeanZero form accepts any finite dt, as it always has (dt only scales the updates); the
   // physics step of the MeanDynamics form needs dt > 0, as gprx_vi_step does.
   if (!build_mech(mech, a.mech) || steps < 0 || ngroups < 1 || T < 0 || !std::isfinite(dt) ||
       (vi_regularizer && (!(dt > 0.0) || !std::isfinite(*vi_regularizer))))
     return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / steps / groups / dt" + (vi_regularizer ? " / regularizer" : ""));
+  if (rq && (rq->R < 0 || rq->steps_per_launch < 0)) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad R / steps_per_launch");
   if (T == 0) return GPRX_OK;
   if (!batches || !slots || !traj_group || !start || !final_state) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  if (rq)
+    if (int rc = rec_check(c, fn, *rq, steps, T)) return rc;
   // coordinates (q, qdot) per mechanism: P1 theta; P2 theta1, theta2 (relative); CP x, theta;
   // FB theta1, theta3 -- the angle coordinates get (sin, cos) features when usesin
   const int nc = mech == GPRX_MECH_P1 ? 1 : 2;
@@ -1675,6 +1747,7 @@ static int rollout_min_call(gprx_ctx* c, const std::string& fn, const char* stat
   RolloutIo io;
   io.sw = (size_t)T * 2 * nc * sizeof(double);
   io.extra = {{status, sizeof(int), 0}, {vi_status, sizeof(int), 0}};
+  if (rq) rec_extras(io, *rq, 2 * (size_t)nc);
   if ((rc = rollout_upload(c, io, gps, T, traj_group, start, a))) return rc;
   a.T = T;
   a.nc = nc;
@@ -1691,11 +1764,25 @@ static int rollout_min_call(gprx_ctx* c, const std::string& fn, const char* stat
   a.status = io.dev<int>(0);
   if (vi_regularizer)  // newton! as gprx_vi_step's callers run it (gprx/projection.py vi_step)
     a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? io.dev<int>(1) : nullptr};
-  timed(c, c->stream, stat, np * steps * (3.0 * dobs + 24.0), np * steps * (dobs + 1) * 8.0, [&] {
-    if (vi_regularizer) gprx::launch_rollout_min_md(a, c->dist_mode, c->stream);
-    else gprx::launch_rollout(a, c->dist_mode, c->stream);
-  });
-  return rollout_download(c, io, T, final_state);
+  const double flops = np * (3.0 * dobs + 24.0), bytes = np * (dobs + 1) * 8.0;  // per step
+  if (!rq) {
+    timed(c, c->stream, stat, flops * steps, bytes * steps, [&] {
+      if (vi_regularizer) gprx::launch_rollout_min_md(a, c->dist_mode, c->stream);
+      else gprx::launch_rollout(a, c->dist_mode, c->stream);
+    });
+    return rollout_download(c, io, T, final_state);
+  }
+  if ((rc = rec_upload(c, io, *rq, T, a.rr))) return rc;
+  const int spl = rq->steps_per_launch > 0 ? rq->steps_per_launch : rec_default_spl(vi_regularizer ? REC_MIN_MD : REC_MIN, T);
+  if (vi_regularizer) {
+    rc = rec_launches(c, stat, a, spl, flops, bytes, gprx::launch_rollout_min_md_rec);
+  } else {
+    gprx::RolloutRecArgs z{};
+    static_cast<gprx::RolloutArgs&>(z) = a;
+    z.rr = a.rr;
+    rc = rec_launches(c, stat, z, spl, flops, bytes, gprx::launch_rollout_rec);
+  }
+  return rc ? rc : rollout_download(c, io, T, final_state);
 }
 
 int gprx_rollout_min(gprx_ctx* c, int mech, int usesin, double dt, int steps, int ngroups,
@@ -1714,21 +1801,25 @@ int gprx_rollout_min_md(gprx_ctx* c, int mech, int usesin, double dt, int steps,
 
 // ---- rollout in maximal coordinates ------------------------------------------------------------
 // gprx_rollout_max (vi_regularizer null: MeanZero GPs, k_rollout_max) and gprx_rollout_max_md (the
-// physics mean per step, k_rollout_max<., RolloutMaxMdArgs>): one validation, scratch layout and launch
+// physics mean per step, k_rollout_max<., RolloutMaxMdArgs>): one validation, scratch layout and launch;
+// with rq the recorded forms (gprx_rollout_max_rec, gprx_rollout_max_md_rec), as rollout_min_call
 static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat, int mech, double dt, int steps, double regularizer,
                             const double* vi_regularizer, int ngroups, gprx_batch* const* batches, const int* slots, int G,
                             const int* vw_idx1, int T, const int* traj_group, const double* start, double* final_state,
-                            double* proj_err, int* status, int* vi_status) {
+                            double* proj_err, int* status, int* vi_status, const RecReq* rq = nullptr) {
   if (!c) return GPRX_INVALID_ARGUMENT;
   gprx::MechDev M;
   if (!build_mech(mech, M) || steps < 0 || ngroups < 1 || T < 0 || G < 1 || G > gprx::PJ_MAXG || !(dt > 0.0) ||
       !std::isfinite(regularizer) || (vi_regularizer && !std::isfinite(*vi_regularizer)))
     return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad mechanism / steps / groups / G / dt / regularizer");
+  if (rq && (rq->R < 0 || rq->steps_per_launch < 0)) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": bad R / steps_per_launch");
   if (T == 0) return GPRX_OK;
   if (!batches || !slots || !vw_idx1 || !traj_group || !start || !final_state)
     return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  if (rq)
+    if (int rc = rec_check(c, fn, *rq, steps, T)) return rc;
   const int d = 13 * M.nb;
-  gprx::RolloutMaxMdArgs a{};
+  gprx::RolloutMaxMdRecArgs a{};  // every form's arguments: each launcher takes the part it knows
   for (int g = 0; g < G; ++g) {
     const int k = (vw_idx1[g] - 1) % 13;
     if (vw_idx1[g] < 1 || vw_idx1[g] > d || k < 7)
@@ -1745,6 +1836,7 @@ static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat
   RolloutIo io;
   io.sw = (size_t)T * d * sizeof(double);
   io.extra = {{proj_err, sizeof(double), 0}, {status, sizeof(int), 0}, {vi_status, sizeof(int), 0}};
+  if (rq) rec_extras(io, *rq, (size_t)d);
   if ((rc = rollout_upload(c, io, gps, T, traj_group, start, a))) return rc;
   a.mech = M;
   a.dt = dt;
@@ -1759,11 +1851,25 @@ static int rollout_max_call(gprx_ctx* c, const std::string& fn, const char* stat
   a.status = io.dev<int>(1);
   if (vi_regularizer)  // newton! as gprx_vi_step's callers run it (gprx/projection.py vi_step)
     a.vi = gprx::RolloutViArgs{*vi_regularizer, 1e-10, 9.81, 100, vi_status ? io.dev<int>(2) : nullptr};
-  timed(c, c->stream, stat, np * steps * (3.0 * d + 24.0), np * steps * (d + 1) * 8.0, [&] {
-    if (vi_regularizer) gprx::launch_rollout_max_md(a, c->dist_mode, c->stream);
-    else gprx::launch_rollout_max(a, c->dist_mode, c->stream);
-  });
-  return rollout_download(c, io, T, final_state);
+  const double flops = np * (3.0 * d + 24.0), bytes = np * (d + 1) * 8.0;  // per step
+  if (!rq) {
+    timed(c, c->stream, stat, flops * steps, bytes * steps, [&] {
+      if (vi_regularizer) gprx::launch_rollout_max_md(a, c->dist_mode, c->stream);
+      else gprx::launch_rollout_max(a, c->dist_mode, c->stream);
+    });
+    return rollout_download(c, io, T, final_state);
+  }
+  if ((rc = rec_upload(c, io, *rq, T, a.rr))) return rc;
+  const int spl = rq->steps_per_launch > 0 ? rq->steps_per_launch : rec_default_spl(vi_regularizer ? REC_MAX_MD : REC_MAX, T);
+  if (vi_regularizer) {
+    rc = rec_launches(c, stat, a, spl, flops, bytes, gprx::launch_rollout_max_md_rec);
+  } else {
+    gprx::RolloutMaxRecArgs z{};
+    static_cast<gprx::RolloutMaxArgs&>(z) = a;
+    z.rr = a.rr;
+    rc = rec_launches(c, stat, z, spl, flops, bytes, gprx::launch_rollout_max_rec);
+  }
+  return rc ? rc : rollout_download(c, io, T, final_state);
 }
 
 int gprx_rollout_max(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups,
@@ -1779,6 +1885,42 @@ int gprx_rollout_max_md(gprx_ctx* c, int mech, double dt, int steps, double regu
                         int* vi_status) {
   return rollout_max_call(c, "gprx_rollout_max_md", "rollout_max_md", mech, dt, steps, regularizer, &vi_regularizer, ngroups,
                           batches, slots, G, vw_idx1, T, traj_group, start, final_state, proj_err, status, vi_status);
+}
+
+// ---- the recorded rollouts: the same calls in launches of at most steps_per_launch steps --------
+int gprx_rollout_min_rec(gprx_ctx* c, int mech, int usesin, double dt, int steps, int ngroups, gprx_batch* const* batches,
+                         const int* slots, int T, const int* traj_group, const double* start, double* final_state, int R,
+                         const int* rec, int steps_per_launch, double* traj) {
+  const RecReq q{R, rec, steps_per_launch, traj};
+  return rollout_min_call(c, "gprx_rollout_min_rec", "rollout_rec", mech, usesin, dt, steps, nullptr, ngroups, batches, slots, T,
+                          traj_group, start, final_state, nullptr, nullptr, &q);
+}
+
+int gprx_rollout_min_md_rec(gprx_ctx* c, int mech, int usesin, double dt, int steps, double vi_regularizer, int ngroups,
+                            gprx_batch* const* batches, const int* slots, int T, const int* traj_group, const double* start,
+                            double* final_state, int* status, int* vi_status, int R, const int* rec, int steps_per_launch,
+                            double* traj) {
+  const RecReq q{R, rec, steps_per_launch, traj};
+  return rollout_min_call(c, "gprx_rollout_min_md_rec", "rollout_min_md_rec", mech, usesin, dt, steps, &vi_regularizer, ngroups,
+                          batches, slots, T, traj_group, start, final_state, status, vi_status, &q);
+}
+
+int gprx_rollout_max_rec(gprx_ctx* c, int mech, double dt, int steps, double regularizer, int ngroups, gprx_batch* const* batches,
+                         const int* slots, int G, const int* vw_idx1, int T, const int* traj_group, const double* start,
+                         double* final_state, double* proj_err, int* status, int R, const int* rec, int steps_per_launch,
+                         double* traj) {
+  const RecReq q{R, rec, steps_per_launch, traj};
+  return rollout_max_call(c, "gprx_rollout_max_rec", "rollout_max_rec", mech, dt, steps, regularizer, nullptr, ngroups, batches,
+                          slots, G, vw_idx1, T, traj_group, start, final_state, proj_err, status, nullptr, &q);
+}
+
+int gprx_rollout_max_md_rec(gprx_ctx* c, int mech, double dt, int steps, double regularizer, double vi_regularizer, int ngroups,
+                            gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1, int T,
+                            const int* traj_group, const double* start, double* final_state, double* proj_err, int* status,
+                            int* vi_status, int R, const int* rec, int steps_per_launch, double* traj) {
+  const RecReq q{R, rec, steps_per_launch, traj};
+  return rollout_max_call(c, "gprx_rollout_max_md_rec", "rollout_max_md_rec", mech, dt, steps, regularizer, &vi_regularizer,
+                          ngroups, batches, slots, G, vw_idx1, T, traj_group, start, final_state, proj_err, status, vi_status, &q);
 }
 
 gprx_batch* gprx_gp_batch(gprx_gp* gp) { return gp ? gp->batch : nullptr; }

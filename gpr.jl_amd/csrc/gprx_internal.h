@@ -213,6 +213,35 @@ struct RolloutMinMdArgs : RolloutArgs {
   int* status;          // T: 0 ok, 2 failed physics mean
   RolloutViArgs vi;
 };
+// The recording, resumable forms of the four rollouts (the *RecArgs instantiations of k_rollout_max
+// and k_rollout): one launch takes steps [step0, step0 + nsteps) of the call's `steps`, writes the
+// records whose storage index (1 = the start, j = after j - 1 steps) it reaches, and, unless it is
+// the last, stores what the step loop and the closing update read on entry; the next launch takes
+// that up again.  The last launch (step0 + nsteps = steps) writes the usual outputs.  The
+// one-launch argument structs, and with them those kernels, are what they were.
+struct RolloutRec {
+  int R, step0, nsteps;
+  const int* rec;   // T x R non-decreasing 1-based storage indices (null when R = 0)
+  double* traj;     // T x R rows: the CState (13 nb) or (q_old, qdot_old) per coordinate (2 nc)
+  int* cursor;      // T: records written so far
+  double* carry;    // T x ROLLOUT_CARRY doubles
+  int* icarry;      // T x 2: status / failed, OR of the physics statuses
+};
+struct RolloutMaxRecArgs : RolloutMaxArgs {
+  RolloutRec rr;
+};
+struct RolloutMaxMdRecArgs : RolloutMaxMdArgs {
+  RolloutRec rr;
+};
+struct RolloutRecArgs : RolloutArgs {
+  RolloutRec rr;
+};
+struct RolloutMinMdRecArgs : RolloutMinMdArgs {
+  RolloutRec rr;
+};
+// doubles a trajectory carries from launch to launch.  Maximal: [obs 13 | xk 3 | qk 4 | s 6] per
+// body, then the projection-error sum.  Minimal: (q_old, qdot_old, q_cur) per coordinate.
+constexpr int ROLLOUT_CARRY = 26 * PJ_MAXB + 1;
 // One variational-integrator step (ConstrainedDynamics 0.7.4 newton!, restated in gprx/vi.py) for T
 // independent states: the MeanDynamics prior mean (src/mDynamics.jl:41-60).
 struct ViArgs {
@@ -250,6 +279,10 @@ void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s);
 void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_max_rec(const RolloutMaxRecArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_max_md_rec(const RolloutMaxMdRecArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_rec(const RolloutRecArgs& a, int dist_mode, hipStream_t s);
+void launch_rollout_min_md_rec(const RolloutMinMdRecArgs& a, int dist_mode, hipStream_t s);
 
 // ---- device helpers that use no device global, shared by gprx_kernels.hip and gprx_projection.hip
 // (gprx_device.h holds the ones that do and belongs to gprx_kernels.hip alone) --------------------

@@ -860,11 +860,47 @@ __host__ __device__ inline size_t md_mat_doubles(int nb, int nd) {
   return pj > vi ? pj : vi;
 }
 template <class Args>
-constexpr bool is_md = std::is_same_v<Args, RolloutMaxMdArgs> || std::is_same_v<Args, RolloutMinMdArgs>;
+constexpr bool is_md = std::is_base_of_v<RolloutMaxMdArgs, Args> || std::is_base_of_v<RolloutMinMdArgs, Args>;
+// The recording, resumable forms (RolloutRec, gprx_internal.h): what they add stands in `if constexpr
+// (is_rec<Args>)`, so the one-launch instantiations keep their instructions (compared in the
+// disassembly) and each step body is stated once.
+template <class Args>
+constexpr bool is_rec = std::is_same_v<Args, RolloutMaxRecArgs> || std::is_same_v<Args, RolloutMaxMdRecArgs> ||
+                        std::is_same_v<Args, RolloutRecArgs> || std::is_same_v<Args, RolloutMinMdRecArgs>;
+// The records a launch has reached: rows of w doubles, row(i) the i-th, for every record whose storage
+// index is at most `idx`; the whole workgroup calls (r and next are the same on every thread).
+template <int NT, class Row>
+__device__ __forceinline__ void rec_write(const RolloutRec& rr, int t, int w, int idx, int& r, int& next, Row row) {
+  while (r < rr.R && next <= idx) {
+    double* o = rr.traj + ((size_t)t * rr.R + r) * w;
+    for (int i = threadIdx.x; i < w; i += NT) o[i] = row(i);
+    ++r;
+    if (r < rr.R) next = rr.rec[(size_t)t * rr.R + r];
+  }
+}
+// NaN in every record from the cursor on: the trajectory has stopped
+template <int NT>
+__device__ __forceinline__ void rec_nan(const RolloutRec& rr, int t, int w, int& r) {
+  for (; r < rr.R; ++r) {
+    double* o = rr.traj + ((size_t)t * rr.R + r) * w;
+    for (int i = threadIdx.x; i < w; i += NT) o[i] = NAN;
+  }
+}
+// the steps of a launch: all of them, or [step0, step0 + nsteps) of a recorded form
+template <class Args>
+__device__ __forceinline__ int step_first(const Args& a) {
+  if constexpr (is_rec<Args>) return a.rr.step0;
+  else return 0;
+}
+template <class Args>
+__device__ __forceinline__ int step_end(const Args& a) {
+  if constexpr (is_rec<Args>) return a.rr.step0 + a.rr.nsteps < a.steps ? a.rr.step0 + a.rr.nsteps : a.steps;
+  else return a.steps;
+}
 template <int MODE, class Args>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(is_md<Args> ? 1 : 4, is_md<Args> ? 2 : 4)))
 void k_rollout_max(Args a) {
-  constexpr bool MD = is_md<Args>;
+  constexpr bool MD = is_md<Args>, REC = is_rec<Args>;
   constexpr int NT = 256, NW = NT / 64;
   __shared__ PState P;
   __shared__ double obs[13 * PJ_MAXB];
@@ -893,7 +929,39 @@ void k_rollout_max(Args a) {
     P.status = 0;
   }
   __syncthreads();
-  for (int step = 0; step < a.steps && P.status == 0; ++step) {
+  [[maybe_unused]] int rcur = 0, rnext = 0;  // the record cursor and the storage index it waits for
+  if constexpr (REC) {
+    if (a.rr.step0 > 0) {
+      // What the loop and the closing update read on entry, as the last launch left it, over the
+      // start's: the CState (obs, and in P), the discrete pose, the solution twists, the error sum
+      // and the statuses.  The pose is carried, not rebuilt by set_states: that is the same algebra,
+      // not the same roundings.
+      const double* cy = a.rr.carry + (size_t)t * ROLLOUT_CARRY;
+      for (int i = tid; i < d; i += NT) {
+        const double v = cy[i];
+        const int b = i / 13, k = i - 13 * b;
+        obs[i] = v;
+        if (k < 3) P.xc[b][k] = v;
+        else if (k < 7) P.qc[b][k - 3] = v;
+        else if (k < 10) P.vc[b][k - 7] = v;
+        else P.wc[b][k - 10] = v;
+      }
+      for (int i = tid; i < 3 * nb; i += NT) P.xk[i / 3][i % 3] = cy[d + i];
+      for (int i = tid; i < 4 * nb; i += NT) P.qk[i / 4][i % 4] = cy[d + 3 * nb + i];
+      for (int i = tid; i < n6; i += NT) P.s[i] = cy[d + 7 * nb + i];
+      if (tid == 0) {
+        perr_s = cy[d + 7 * nb + n6];
+        P.status = a.rr.icarry[2 * t];
+      }
+      if constexpr (MD) vis = a.rr.icarry[2 * t + 1];
+      rcur = a.rr.cursor[t];
+      __syncthreads();
+    }
+    if (rcur < a.rr.R) rnext = a.rr.rec[(size_t)t * a.rr.R + rcur];
+  }
+  for (int step = step_first(a); step < step_end(a) && P.status == 0; ++step) {
+    // obs is the CState after `step` steps, storage index step + 1 (it changes after the next barrier)
+    if constexpr (REC) rec_write<NT>(a.rr, t, d, step + 1, rcur, rnext, [&](int i) { return obs[i]; });
     // ---- mu_g = sum_j sf2 exp(-r_j / 2) alpha_j at the current CState (predict_y means)
     for (int g = 0; g < G; ++g) {
       const RolloutGP Gp = gp[g];
@@ -954,6 +1022,29 @@ void k_rollout_max(Args a) {
       for (int i = l; i < d; i += 64) obs[i] = cstate_at(P, i);
     }
     __syncthreads();
+  }
+  if constexpr (REC) {
+    // the state the loop ended at, index step_end + 1 (the next launch's first, or the last of all); a
+    // trajectory that stopped has NaN from the failed step onward and keeps its one-launch outputs
+    if (P.status == 0) {
+      rec_write<NT>(a.rr, t, d, step_end(a) + 1, rcur, rnext, [&](int i) { return obs[i]; });
+    } else {
+      rec_nan<NT>(a.rr, t, d, rcur);
+    }
+    if (step_end(a) < a.steps) {
+      double* cy = a.rr.carry + (size_t)t * ROLLOUT_CARRY;
+      for (int i = tid; i < d; i += NT) cy[i] = obs[i];
+      for (int i = tid; i < 3 * nb; i += NT) cy[d + i] = P.xk[i / 3][i % 3];
+      for (int i = tid; i < 4 * nb; i += NT) cy[d + 3 * nb + i] = P.qk[i / 4][i % 4];
+      for (int i = tid; i < n6; i += NT) cy[d + 7 * nb + i] = P.s[i];
+      if (tid == 0) {
+        cy[d + 7 * nb + n6] = perr_s;
+        a.rr.cursor[t] = rcur;
+        a.rr.icarry[2 * t] = P.status;
+        a.rr.icarry[2 * t + 1] = vis;
+      }
+      return;
+    }
   }
   if (w == 0) {
     update_state(P, nb, a.dt, l);  // the closing updatestate! (predictdynamics.jl:20)
@@ -1067,10 +1158,15 @@ static __device__ __forceinline__ void min_cstate_body(int mech, int b, double a
 __device__ __forceinline__ double pick3(const double (&e)[3], int i) {
   return i == 0 ? e[0] : (i == 1 ? e[1] : (i == 2 ? e[2] : 0.0));
 }
+// entry i of a record, (q_old, qdot_old) per coordinate, from copies of the four values (selects: a
+// register array indexed by a lane-dependent value, or one a lambda refers to, would live in scratch memory)
+__device__ __forceinline__ double min_row(double q0, double v0, double q1, double v1, int i) {
+  return (i & 1) ? (i >> 1 ? v1 : v0) : (i >> 1 ? q1 : q0);
+}
 
 template <int MODE, class Args>
 __global__ __launch_bounds__(256) void k_rollout(Args a) {
-  constexpr bool MD = is_md<Args>;
+  constexpr bool MD = is_md<Args>, REC = is_rec<Args>;
   constexpr int NT = 256, NW = NT / 64, U = 4;  // U training points per thread in flight
   __shared__ double red[2][NW][2];
   [[maybe_unused]] __shared__ PState Q;  // the physics mean's state, (sq1 I - [w1 x]) J w1 and CState
@@ -1089,7 +1185,29 @@ __global__ __launch_bounds__(256) void k_rollout(Args a) {
   const int w0 = s0 ? 3 : 2;
   [[maybe_unused]] int vis = 0;
   bool failed = false;
-  for (int step = 0; step < a.steps; ++step) {
+  [[maybe_unused]] int rcur = 0, rnext = 0;  // the record cursor and the storage index it waits for
+  if constexpr (REC) {
+    if (a.rr.step0 > 0) {  // the coordinates and the statuses as the last launch left them
+      const double* cy = a.rr.carry + (size_t)t * ROLLOUT_CARRY;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        qo[c] = cy[3 * c];
+        vo[c] = cy[3 * c + 1];
+        qc[c] = cy[3 * c + 2];
+      }
+      rcur = a.rr.cursor[t];
+      failed = a.rr.icarry[2 * t] != 0;
+      vis = a.rr.icarry[2 * t + 1];
+    }
+    if (rcur < a.rr.R) rnext = a.rr.rec[(size_t)t * a.rr.R + rcur];
+  }
+  for (int step = step_first(a); step < step_end(a); ++step) {
+    if constexpr (REC) {
+      if (failed) break;  // the trajectory has stopped in an earlier launch (the same on every thread)
+      // (q_old, qdot_old) is the state after `step` steps, storage index step + 1
+      const double q0 = qo[0], v0 = vo[0], q1 = qo[1], v1 = vo[1];
+      rec_write<NT>(a.rr, t, 2 * nc, step + 1, rcur, rnext, [=](int i) { return min_row(q0, v0, q1, v1, i); });
+    }
     double e0[3], e1[3];
     e0[0] = s0 ? sin(qo[0]) : qo[0];
     e0[1] = s0 ? cos(qo[0]) : vo[0];
@@ -1190,6 +1308,26 @@ __global__ __launch_bounds__(256) void k_rollout(Args a) {
       qc[c] = __dadd_rn(qc[c], __dmul_rn(pred[c], a.dt));
     }
   }
+  if constexpr (REC) {
+    // the state the loop ended at, index step_end + 1; NaN from a failed step onward
+    const double q0 = qo[0], v0 = vo[0], q1 = qo[1], v1 = vo[1];
+    if (!failed) rec_write<NT>(a.rr, t, 2 * nc, step_end(a) + 1, rcur, rnext, [=](int i) { return min_row(q0, v0, q1, v1, i); });
+    else rec_nan<NT>(a.rr, t, 2 * nc, rcur);
+    if (step_end(a) < a.steps) {
+      if (tid == 0) {
+        double* cy = a.rr.carry + (size_t)t * ROLLOUT_CARRY;
+        for (int c = 0; c < 2; ++c) {
+          cy[3 * c] = qo[c];
+          cy[3 * c + 1] = vo[c];
+          cy[3 * c + 2] = qc[c];
+        }
+        a.rr.cursor[t] = rcur;
+        a.rr.icarry[2 * t] = failed ? 2 : 0;
+        a.rr.icarry[2 * t + 1] = vis;
+      }
+      return;
+    }
+  }
   if (tid == 0) {
     for (int c = 0; c < nc; ++c) {
       a.out[(size_t)t * 2 * nc + 2 * c] = failed ? NAN : qc[c];
@@ -1211,19 +1349,19 @@ void launch_vi_step(const ViArgs& a, hipStream_t s) {
 void launch_simulate(const SimArgs& a, hipStream_t s) {
   if (a.T > 0) hipLaunchKernelGGL(k_simulate, dim3(a.T), dim3(64), vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s, a);
 }
-void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s) {
+template <class Args>
+static void launch_rollout_max_t(const Args& a, int dist_mode, hipStream_t s) {
   if (a.T <= 0) return;
-  const size_t lds = pj_lds_bytes(a.mech.nb, a.mech.nd);
-  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, RolloutMaxArgs>), dim3(a.T), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((k_rollout_max<1, RolloutMaxArgs>), dim3(a.T), dim3(256), lds, s, a);
+  // MeanDynamics: [the larger of the projection's F / A and the solve's matrix + Gpos | the solve's PState | mom1]
+  const size_t lds = is_md<Args> ? md_mat_doubles(a.mech.nb, a.mech.nd) * sizeof(double) + sizeof(PState) + sizeof(double) * 3 * PJ_MAXB
+                                 : pj_lds_bytes(a.mech.nb, a.mech.nd);
+  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, Args>), dim3(a.T), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((k_rollout_max<1, Args>), dim3(a.T), dim3(256), lds, s, a);
 }
-void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s) {
-  if (a.T <= 0) return;
-  // [the larger of the projection's F / A and the solve's matrix + Gpos | the solve's PState | mom1]
-  const size_t lds = md_mat_doubles(a.mech.nb, a.mech.nd) * sizeof(double) + sizeof(PState) + sizeof(double) * 3 * PJ_MAXB;
-  if (dist_mode == 0) hipLaunchKernelGGL((k_rollout_max<0, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((k_rollout_max<1, RolloutMaxMdArgs>), dim3(a.T), dim3(256), lds, s, a);
-}
+void launch_rollout_max(const RolloutMaxArgs& a, int dist_mode, hipStream_t s) { launch_rollout_max_t(a, dist_mode, s); }
+void launch_rollout_max_md(const RolloutMaxMdArgs& a, int dist_mode, hipStream_t s) { launch_rollout_max_t(a, dist_mode, s); }
+void launch_rollout_max_rec(const RolloutMaxRecArgs& a, int dist_mode, hipStream_t s) { launch_rollout_max_t(a, dist_mode, s); }
+void launch_rollout_max_md_rec(const RolloutMaxMdRecArgs& a, int dist_mode, hipStream_t s) { launch_rollout_max_t(a, dist_mode, s); }
 // 256 threads per trajectory for every T (measured: 512 is 0.04 ms faster for 100 trajectories, 256 is
 // 1.4x faster for 3200; a fixed size keeps each trajectory's sums independent of T)
 template <class Args>
@@ -1234,6 +1372,10 @@ static void launch_rollout_min(const Args& a, int dist_mode, size_t lds, hipStre
 }
 void launch_rollout(const RolloutArgs& a, int dist_mode, hipStream_t s) { launch_rollout_min(a, dist_mode, 0, s); }
 void launch_rollout_min_md(const RolloutMinMdArgs& a, int dist_mode, hipStream_t s) {
+  launch_rollout_min(a, dist_mode, vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s);
+}
+void launch_rollout_rec(const RolloutRecArgs& a, int dist_mode, hipStream_t s) { launch_rollout_min(a, dist_mode, 0, s); }
+void launch_rollout_min_md_rec(const RolloutMinMdRecArgs& a, int dist_mode, hipStream_t s) {
   launch_rollout_min(a, dist_mode, vi_lds_doubles(a.mech.nb, a.mech.nd) * sizeof(double), s);
 }
 

@@ -106,6 +106,15 @@ SIGNATURES = {
                                       C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip]),
     "gprx_rollout_min_md": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _ip,
                                       C.c_int, _ip, _dp, _dp, _ip, _ip]),
+    # the recorded rollouts: the one-launch call's arguments + (R, rec, steps_per_launch, traj)
+    "gprx_rollout_min_rec": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(_vp), _ip, C.c_int,
+                                       _ip, _dp, _dp, C.c_int, _ip, C.c_int, _dp]),
+    "gprx_rollout_min_md_rec": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _ip,
+                                          C.c_int, _ip, _dp, _dp, _ip, _ip, C.c_int, _ip, C.c_int, _dp]),
+    "gprx_rollout_max_rec": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _ip, C.c_int,
+                                       _ip, C.c_int, _ip, _dp, _dp, _dp, _ip, C.c_int, _ip, C.c_int, _dp]),
+    "gprx_rollout_max_md_rec": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_vp),
+                                          _ip, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, C.c_int, _ip, C.c_int, _dp]),
     "gprx_cstate_pack": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gprx_select_outputs": (C.c_int, [_dp, C.c_int, C.c_int, _ip, C.c_int, _dp]),
 }

@@ -5,7 +5,9 @@ gprx_rollout_max).
 of a predicted twist (v, w per body) onto the mechanism's joint constraints, for many mechanism
 states in one launch.  `predictdynamics` is examples/utils/predictdynamics.jl:7-22 for many test
 trajectories in one launch: per step the G GPs' mean predictions at the current CState, getvw,
-projectv! and updatestate!, all on the device.
+projectv! and updatestate!, all on the device.  `predictdynamics_rec` / `predictdynamics_md_rec` are
+the same rollouts keeping the CState at the steps the caller names, in launches of bounded length
+(gprx_rollout_max_rec, gprx_rollout_max_md_rec; examples/energy.jl's predictedstates).
 
 Mechanisms are the experiments' (examples/utils/data/simulations.jl): P1 pendulum, P2 double
 pendulum, CP cart-pole, FB four-bar (which the experiments project with regularizer=1e-10,
@@ -139,10 +141,12 @@ def predictdynamics(mech: str, groups, start, steps: int, vw_indices, regularize
     return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=False)[:3]
 
 
-def _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md, vi_regularizer=None):
+def _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md, vi_regularizer=None,
+                     record=None):
     """predictdynamics (md False: MeanZero GPs) and predictdynamics_md: (final CStates, projection
-    error, status, vi_status), the last None for MeanZero GPs."""
-    from .rollout import _device_args, _slot_ref, _slot_ref_md
+    error, status, vi_status), the last None for MeanZero GPs.  record = (rec, steps_per_launch): the
+    recorded forms, with the trajectory (T, R, 13 nb) ahead of the four."""
+    from .rollout import _device_args, _record_args, _slot_ref, _slot_ref_md
 
     if mech not in MECH:
         raise ValueError(f"Experiment {mech} not supported!")
@@ -152,6 +156,8 @@ def _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_g
     if S.shape != (T, 13 * nb):
         raise ValueError(f"start must be (T, {13 * nb})")
     G = len(vw_indices)
+    rc, traj, rtail = _record_args(record[0], T, steps, record[1], 13 * nb) if record else (None, None, ())
+    pre = (traj,) if record else ()
     ref = (lambda g, k: _slot_ref_md(g, mech, "max", k)) if md else (lambda g, k: _slot_ref(g))
     batches, slots, tg, ctx = _device_args(groups, G, f"each group needs {G} GPs (one per vw index)", T, traj_group, ref, ctx)
     vwi = np.ascontiguousarray(vw_indices, dtype=np.int32)
@@ -162,14 +168,16 @@ def _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_g
     head = (ctx.h, MECH[mech], float(dt), int(steps), reg)
     tail = (len(groups), batches, L.iptr(slots), G, L.iptr(vwi), T, L.iptr(tg), L.dptr(S), L.dptr(out), L.dptr(pe), L.iptr(st))
     if not md:
-        L.check(L.lib.gprx_rollout_max(*head, *tail), ctx.h)
-        return out, pe, st, None
+        fn = L.lib.gprx_rollout_max_rec if record else L.lib.gprx_rollout_max
+        L.check(fn(*head, *tail, *rtail), ctx.h)
+        return pre + (out, pe, st, None)
     from . import vi
 
     vreg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
     vst = np.empty(T, dtype=np.int32)
-    L.check(L.lib.gprx_rollout_max_md(*head, vreg, *tail, L.iptr(vst)), ctx.h)
-    return out, pe, st, vst
+    fn = L.lib.gprx_rollout_max_md_rec if record else L.lib.gprx_rollout_max_md
+    L.check(fn(*head, vreg, *tail, L.iptr(vst), *rtail), ctx.h)
+    return pre + (out, pe, st, vst)
 
 
 def predictdynamics_md(mech: str, groups, start, steps: int, vw_indices, regularizer: float | None = None,
@@ -183,6 +191,28 @@ def predictdynamics_md(mech: str, groups, start, steps: int, vw_indices, regular
     NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
     return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=True,
                             vi_regularizer=vi_regularizer)
+
+
+def predictdynamics_rec(mech: str, groups, start, steps: int, vw_indices, rec=None, regularizer: float | None = None,
+                        traj_group=None, dt: float = DT, steps_per_launch: int = 0, ctx: Context | None = None):
+    """predictdynamics that keeps the trajectory, in launches of at most steps_per_launch steps (0: the
+    library's default; gprx_rollout_max_rec).  rec: None (every index, 1 .. steps + 1), (R,) for all
+    trajectories or (T, R): non-decreasing 1-based storage indices, 1 = the start, j = the state after
+    j - 1 steps.  Returns (trajectory (T, R, 13 nb): oldstates = CState(mechanism) of
+    predictdynamics.jl:18 at each index, examples/energy.jl's predictedstates, NaN after a step that
+    failed; then predictdynamics' three, bit for bit, whatever rec and steps_per_launch)."""
+    return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=False,
+                            record=(rec, steps_per_launch))[:4]
+
+
+def predictdynamics_md_rec(mech: str, groups, start, steps: int, vw_indices, rec=None, regularizer: float | None = None,
+                           vi_regularizer: float | None = None, traj_group=None, dt: float = DT, steps_per_launch: int = 0,
+                           ctx: Context | None = None):
+    """predictdynamics_md that keeps the trajectory (gprx_rollout_max_md_rec); rec and steps_per_launch
+    as predictdynamics_rec's.  Returns (trajectory (T, R, 13 nb); then predictdynamics_md's four, bit
+    for bit)."""
+    return _predictdynamics(mech, groups, start, steps, vw_indices, regularizer, traj_group, dt, ctx, md=True,
+                            vi_regularizer=vi_regularizer, record=(rec, steps_per_launch))
 
 
 def _default_ctx():

@@ -16,6 +16,8 @@ Coordinates (startobservation layout, predictdynamics.jl:40,54,71,86):
 GP inputs per step: that vector, or with usesin (sin q, cos q, qdot) for the angle coordinates.
 rollout_min / predictdynamicsmin take MeanZero GPs; MeanDynamics GPs, whose mean is a physics solve per
 step, roll out through rollout_min_md (gprx_rollout_min_md: the solve runs in the same launch).
+rollout_min_rec / rollout_min_md_rec are the same rollouts keeping (q_old, qdot_old) at the steps the
+caller names, in launches of bounded length (gprx_rollout_min_rec, gprx_rollout_min_md_rec).
 """
 from __future__ import annotations
 
@@ -65,9 +67,46 @@ def _device_args(groups, n: int, what: str, T: int, traj_group, ref, ctx):
     return batches, slots, tg, ctx or refs[0][0].ctx
 
 
-def _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md, vi_regularizer=None):
+def record_indices(rec, T: int, steps: int) -> np.ndarray:
+    """The storage indices of a recorded rollout as the C calls take them, (T, R) int32: rec None
+    (every index, 1 .. steps + 1), (R,) shared by all trajectories, or (T, R).  1-based, as
+    gprx_simulate's: 1 is the start, j the state after j - 1 steps.  ValueError for a wrong shape, an
+    index outside [1, steps + 1] or a decreasing row."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    if rec is None:
+        rec = np.arange(1, steps + 2)
+    rc = np.asarray(rec)
+    if rc.size == 0:
+        rc = rc.astype(np.int32)
+    if rc.dtype.kind not in "iu":
+        raise ValueError("rec must hold integers")
+    if rc.ndim == 1:
+        rc = np.broadcast_to(rc, (T, rc.shape[0]))
+    if rc.ndim != 2 or rc.shape[0] != T:
+        raise ValueError("rec must be None, (R,) or (T, R)")
+    if rc.size and (rc.min() < 1 or rc.max() > steps + 1):
+        raise ValueError(f"rec indices must lie in [1, steps + 1] = [1, {steps + 1}]")
+    if np.any(np.diff(rc, axis=1) < 0):
+        raise ValueError("rec must be non-decreasing per trajectory")
+    return np.ascontiguousarray(rc, dtype=np.int32)
+
+
+def _record_args(rec, T: int, steps: int, steps_per_launch: int, width: int):
+    """(rec (T, R) int32, traj (T, R, width), the C calls' (R, rec, steps_per_launch, traj))."""
+    if int(steps_per_launch) < 0:
+        raise ValueError("steps_per_launch must be >= 1, or 0 for the default")
+    rc = record_indices(rec, T, steps)
+    R = rc.shape[1]
+    traj = np.empty((T, R, width))
+    return rc, traj, (R, L.iptr(rc) if R else None, int(steps_per_launch), L.dptr(traj) if R else None)
+
+
+def _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md, vi_regularizer=None, record=None):
     """rollout_min (md False: MeanZero GPs) and rollout_min_md: (final, status, vi_status), the last
-    two None for MeanZero GPs."""
+    two None for MeanZero GPs.  record = (rec, steps_per_launch): the recorded forms, with the
+    trajectory (T, R, 2nc) ahead of the three."""
     if mech not in MECH:
         raise ValueError(f"Experiment {mech} not supported!")  # predictdynamics.jl:35
     nc = NCOORD[mech]
@@ -78,21 +117,25 @@ def _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md, vi
     if start.shape != (T, 2 * nc):
         raise ValueError(f"start must be (T, {2 * nc})")
     variant = "min_sin" if usesin else "min"
+    rc, traj, rtail = _record_args(record[0], T, steps, record[1], 2 * nc) if record else (None, None, ())
+    pre = (traj,) if record else ()
     ref = (lambda g, k: _slot_ref_md(g, mech, variant, k)) if md else (lambda g, k: _slot_ref(g))
     batches, slots, tg, ctx = _device_args(groups, nc, f"{mech} rollouts use {nc} GP(s) per group", T, traj_group, ref, ctx)
     out = np.empty((T, 2 * nc), dtype=np.float64)
     head = (ctx.h, MECH[mech], 1 if usesin else 0, float(dt), int(steps))
     tail = (len(groups), batches, L.iptr(slots), T, L.iptr(tg), L.dptr(start), L.dptr(out))
     if not md:
-        L.check(L.lib.gprx_rollout_min(*head, *tail), ctx.h)
-        return out, None, None
+        fn = L.lib.gprx_rollout_min_rec if record else L.lib.gprx_rollout_min
+        L.check(fn(*head, *tail, *rtail), ctx.h)
+        return pre + (out, None, None)
     from . import vi
 
     reg = vi.REGULARIZER[mech] if vi_regularizer is None else float(vi_regularizer)
     st = np.empty(T, dtype=np.int32)
     vst = np.empty(T, dtype=np.int32)
-    L.check(L.lib.gprx_rollout_min_md(*head, reg, *tail, L.iptr(st), L.iptr(vst)), ctx.h)
-    return out, st, vst
+    fn = L.lib.gprx_rollout_min_md_rec if record else L.lib.gprx_rollout_min_md
+    L.check(fn(*head, reg, *tail, L.iptr(st), L.iptr(vst), *rtail), ctx.h)
+    return pre + (out, st, vst)
 
 
 def _slot_ref(g):
@@ -133,6 +176,26 @@ def rollout_min_md(mech: str, groups, start, steps: int, usesin: bool = False, d
     MeanDynamics(mech, g + 1, "min" / "min_sin").  Returns (final (T, 2nc), status (T,): 2 = a failed
     physics step, the row is NaN; vi_status (T,): OR of the per-step vi_step statuses)."""
     return _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md=True, vi_regularizer=vi_regularizer)
+
+
+def rollout_min_rec(mech: str, groups, start, steps: int, rec=None, usesin: bool = False, dt: float = DT,
+                    traj_group=None, steps_per_launch: int = 0, ctx: Context | None = None):
+    """rollout_min that keeps the trajectory, in launches of at most steps_per_launch steps (0: the
+    library's default; gprx_rollout_min_rec).  rec: None (every index, 1 .. steps + 1), (R,) for all
+    trajectories or (T, R): non-decreasing 1-based storage indices, 1 = the start, j = after j - 1
+    steps.  Returns (trajectory (T, R, 2nc): (q_old, qdot_old) per coordinate at each index; final
+    (T, 2nc), bit for bit rollout_min's, whatever rec and steps_per_launch)."""
+    return _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md=False, record=(rec, steps_per_launch))[:2]
+
+
+def rollout_min_md_rec(mech: str, groups, start, steps: int, rec=None, usesin: bool = False, dt: float = DT,
+                       vi_regularizer: float | None = None, traj_group=None, steps_per_launch: int = 0,
+                       ctx: Context | None = None):
+    """rollout_min_md that keeps the trajectory (gprx_rollout_min_md_rec); rec and steps_per_launch as
+    rollout_min_rec's.  Returns (trajectory (T, R, 2nc), NaN after a failed physics step; final, status,
+    vi_status as rollout_min_md's, bit for bit)."""
+    return _rollout_min(mech, groups, start, steps, usesin, dt, traj_group, ctx, md=True, vi_regularizer=vi_regularizer,
+                        record=(rec, steps_per_launch))
 
 
 def _rotx_q(th):

@@ -242,6 +242,96 @@ function rollout_max_md(etype::String, gps::Vector{<:GPE}, startobservations::Ve
     return [fin[:, t] for t in 1:T], perr, status, vi_status
 end
 
+# ---- the recorded rollouts (gprx_rollout_*_rec): the trajectory at the storage indices `record`
+# (1-based: 1 the start, j the state after j - 1 steps; a vector for every trajectory or one per
+# trajectory; nothing = every index 1:steps+1), in launches of at most `steps_per_launch` steps (0: the
+# library's default).  The final outputs are those of the one-launch calls.  Like the rest of this
+# file they have not been run.
+function record_matrix(record, T::Integer, steps::Integer)
+    rec = record === nothing ? collect(1:steps+1) : record
+    R = rec isa AbstractVector{<:Integer} ? reduce(hcat, [Vector{Cint}(rec) for _ in 1:T]) : reduce(hcat, [Vector{Cint}(r) for r in rec])
+    size(R, 2) == T || throw(ArgumentError("one record list per trajectory"))
+    all(1 .<= R .<= steps + 1) && all(diff(R, dims=1) .>= 0) || throw(ArgumentError("record: non-decreasing indices in 1:steps+1"))
+    return Matrix{Cint}(R)   # R x T column-major: trajectory t's indices contiguous, the ABI's rec[t*R ...]
+end
+trajectories(traj::Array{Float64,3}) = [[traj[:, r, t] for r in 1:size(traj, 2)] for t in 1:size(traj, 3)]
+
+# predictdynamicsmin keeping (q_old, q̇_old) per coordinate at every recorded index; MeanZero or
+# MeanDynamics GPs.  Returns (trajectories, final, status, vi_status), the last two nothing for MeanZero.
+function rollout_min(etype::String, gps::Vector{<:GPE}, startobservations::Vector{Vector{Float64}}, steps::Integer,
+                     record; usesin::Bool=false, Δt::Real=0.01, steps_per_launch::Integer=0)
+    haskey(MECH, etype) || throw(ArgumentError("Experiment $etype not supported!"))
+    md = !any(gp -> gp.mean isa MeanZero, gps)
+    md || all(gp -> gp.mean isa MeanZero, gps) || error("gprx: a rollout's GPs share one mean type")
+    T = length(startobservations)
+    nc = etype == "P1" ? 1 : 2
+    rec = record_matrix(record, T, steps)
+    R = size(rec, 1)
+    fin, traj = zeros(2nc, T), zeros(2nc, R, T)
+    status, vi_status = zeros(Cint, T), zeros(Cint, T)
+    bs = [ccall((:gprx_gp_batch, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), handle(gp).ptr) for gp in gps]
+    if md
+        rc = ccall((:gprx_rollout_min_md_rec, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cdouble, Cint, Cdouble, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Cint, Ptr{Cint}, Cint, Ptr{Float64}),
+                   context(), MECH[etype], Cint(usesin), Float64(Δt), Cint(steps), vi_regularizer(etype), Cint(1), bs,
+                   zeros(Cint, nc), Cint(T), zeros(Cint, T), reduce(hcat, startobservations), fin, status, vi_status,
+                   Cint(R), rec, Cint(steps_per_launch), traj)
+    else
+        rc = ccall((:gprx_rollout_min_rec, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cdouble, Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                    Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cint}, Cint, Ptr{Float64}),
+                   context(), MECH[etype], Cint(usesin), Float64(Δt), Cint(steps), Cint(1), bs, zeros(Cint, nc),
+                   Cint(T), zeros(Cint, T), reduce(hcat, startobservations), fin, Cint(R), rec, Cint(steps_per_launch), traj)
+    end
+    check(rc, gps)
+    return trajectories(traj), [fin[:, t] for t in 1:T], md ? status : nothing, md ? vi_status : nothing
+end
+
+# predictdynamics (examples/utils/predictdynamics.jl:7-22) for all start CStates of one trial on the
+# device, MeanZero or MeanDynamics GPs; gps[g] predicts CState position vωindices[g].  With the
+# `record` keyword (see above; examples/energy.jl keeps every step: record = 2:steps+1) the CStates
+# `oldstates` of predictdynamics.jl:18 at the recorded indices come first in the returned tuple:
+# ([trajectories,] final CStates, projection errors, status, vi_status (nothing for MeanZero)).
+function predictdynamics(etype::String, gps::Vector{<:GPE}, startobservations::Vector{Vector{Float64}},
+                         steps::Integer, vωindices::Vector{<:Integer}; regularizer::Real=0.0, Δt::Real=0.01,
+                         record=missing, steps_per_launch::Integer=0)
+    haskey(MECH, etype) || throw(ArgumentError("Experiment $etype not supported!"))
+    md = !any(gp -> gp.mean isa MeanZero, gps)
+    md || all(gp -> gp.mean isa MeanZero, gps) || error("gprx: a rollout's GPs share one mean type")
+    length(gps) == length(vωindices) || throw(ArgumentError("one GP per vω index"))
+    T, G = length(startobservations), length(gps)
+    d = length(startobservations[1])
+    keep = record !== missing
+    rec = keep ? record_matrix(record, T, steps) : zeros(Cint, 0, T)
+    R = size(rec, 1)
+    fin, perr, traj = zeros(d, T), zeros(T), zeros(d, R, T)
+    status, vi_status = zeros(Cint, T), zeros(Cint, T)
+    bs = [ccall((:gprx_gp_batch, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), handle(gp).ptr) for gp in gps]
+    recp, trajp = R > 0 ? (pointer(rec), pointer(traj)) : (Ptr{Cint}(C_NULL), Ptr{Float64}(C_NULL))
+    GC.@preserve rec traj begin
+        if md
+            rc = ccall((:gprx_rollout_max_md_rec, LIB), Cint,
+                       (Ptr{Cvoid}, Cint, Cdouble, Cint, Cdouble, Cdouble, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                        Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint},
+                        Cint, Ptr{Cint}, Cint, Ptr{Float64}),
+                       context(), MECH[etype], Float64(Δt), Cint(steps), Float64(regularizer), vi_regularizer(etype), Cint(1), bs,
+                       zeros(Cint, G), Cint(G), Vector{Cint}(vωindices), Cint(T), zeros(Cint, T),
+                       reduce(hcat, startobservations), fin, perr, status, vi_status, Cint(R), recp, Cint(steps_per_launch), trajp)
+        else
+            rc = ccall((:gprx_rollout_max_rec, LIB), Cint,
+                       (Ptr{Cvoid}, Cint, Cdouble, Cint, Cdouble, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Cint, Ptr{Cint},
+                        Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cint, Ptr{Cint}, Cint, Ptr{Float64}),
+                       context(), MECH[etype], Float64(Δt), Cint(steps), Float64(regularizer), Cint(1), bs,
+                       zeros(Cint, G), Cint(G), Vector{Cint}(vωindices), Cint(T), zeros(Cint, T),
+                       reduce(hcat, startobservations), fin, perr, status, Cint(R), recp, Cint(steps_per_launch), trajp)
+        end
+    end
+    check(rc, gps)
+    out = ([fin[:, t] for t in 1:T], perr, status, md ? vi_status : nothing)
+    return keep ? (trajectories(traj), out...) : out
+end
+
 # gprx_opt_options (include/gprx.h): same field order and C layout
 struct OptOptions
     m::Cint

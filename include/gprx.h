@@ -398,6 +398,55 @@ int gprx_rollout_min_md(gprx_ctx* ctx, int mech, int usesin, double dt, int step
                         int T, const int* traj_group, const double* start,
                         double* final_state, int* status, int* vi_status);
 
+/* ---- recorded rollouts: the trajectory step by step, in bounded launches --------------------------
+ * The four rollouts above return the final state only and run every step in one launch.  Each
+ * entry point below takes the arguments of its one-launch counterpart plus R, rec,
+ * steps_per_launch and traj, keeps the trajectory's state after the steps the caller names
+ * (examples/energy.jl keeps all 600 000), and runs as successive launches of at most
+ * steps_per_launch steps, the trajectory's state and record cursor carried in device memory, so
+ * that no launch holds the device for seconds.
+ * rec[t*R ...]: R non-decreasing 1-based storage indices in [1, steps + 1], gprx_simulate's
+ * convention: 1 is the start as given, j the trajectory's state after j - 1 steps, before the
+ * closing updatestate!.  traj[(t*R + r)*w ...] is the row at rec[t*R + r]:
+ *   maximal (w = 13 nb): oldstates = CState(mechanism) of predictdynamics.jl:18, the state the
+ *     GPs are evaluated at in step j (energy.jl's predictedstates);
+ *   minimal (w = 2 nc): (q_old, qdot_old) per coordinate.
+ * R = 0 with rec and traj NULL is allowed: a bounded-launch rollout that records nothing.
+ * The final outputs (final_state, proj_err, status, vi_status) are bit for bit those of the
+ * one-launch entry point for the same arguments, for every steps_per_launch -- a trajectory always
+ * runs all `steps`, wherever its last record lies -- and traj does not depend on
+ * steps_per_launch.  A trajectory that stops (status 1, singular projection; status 2, failed
+ * physics mean) keeps its one-launch outputs (NaN row, status); its records up to the state the
+ * failed step started from are kept and the later ones are NaN; the other trajectories of the call
+ * are not affected.
+ * steps_per_launch >= 1, or 0 for the default: 0.2 s divided by the time one step of the call's T
+ * trajectories takes at the largest shapes the project rolls out (the four-bar, N = 512), lat + T traj
+ * from two measurements on an MI355X, T = 100 and T = 3200 (DESIGN.md section 4 has the figures):
+ * T = 100 gives 56 steps (maximal), 34 (maximal, MeanDynamics), 224 (minimal, MeanDynamics) and
+ * 45 977 (minimal); T = 3200 gives 17, 10, 21 and 6514.
+ * GPRX_INVALID_ARGUMENT: what the one-launch call refuses, R < 0, steps_per_launch < 0, a
+ * decreasing rec or an index out of range, rec or traj NULL with R > 0.  T = 0 is GPRX_OK.  The
+ * records live in the context's scratch buffer until they are copied out: GPRX_OUT_OF_MEMORY when
+ * it cannot be grown to T * R * w doubles.                                                         */
+int gprx_rollout_min_rec(gprx_ctx* ctx, int mech, int usesin, double dt, int steps, int ngroups,
+                         gprx_batch* const* batches, const int* slots, int T, const int* traj_group,
+                         const double* start, double* final_state,
+                         int R, const int* rec, int steps_per_launch, double* traj);
+int gprx_rollout_min_md_rec(gprx_ctx* ctx, int mech, int usesin, double dt, int steps, double vi_regularizer,
+                            int ngroups, gprx_batch* const* batches, const int* slots,
+                            int T, const int* traj_group, const double* start,
+                            double* final_state, int* status, int* vi_status,
+                            int R, const int* rec, int steps_per_launch, double* traj);
+int gprx_rollout_max_rec(gprx_ctx* ctx, int mech, double dt, int steps, double regularizer, int ngroups,
+                         gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1, int T,
+                         const int* traj_group, const double* start, double* final_state, double* proj_err,
+                         int* status, int R, const int* rec, int steps_per_launch, double* traj);
+int gprx_rollout_max_md_rec(gprx_ctx* ctx, int mech, double dt, int steps, double regularizer, double vi_regularizer,
+                            int ngroups, gprx_batch* const* batches, const int* slots, int G, const int* vw_idx1,
+                            int T, const int* traj_group, const double* start,
+                            double* final_state, double* proj_err, int* status, int* vi_status,
+                            int R, const int* rec, int steps_per_launch, double* traj);
+
 /* ---- host-side CState helpers (bit-exact copies) ------------------------------------------ */
 /* out[13*b + 0..12] = [xc(3), qc.w, qc.x, qc.y, qc.z, vc(3), wc(3)] for body b (CState.jl:20,26) */
 int gprx_cstate_pack(int nbodies, const double* xc, const double* qc_wxyz, const double* vc,
