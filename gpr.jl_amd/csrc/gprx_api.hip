@@ -1331,6 +1331,51 @@ static int ctx_scratch(gprx_ctx* c, size_t need, char** base) {
   return GPRX_OK;
 }
 
+// ---- leave-one-out predictions (gprx_loo.h) ------------------------------------------------------
+// Workspace in the context scratch: kinv, mu, var, lp (B x Npad each), logp (B).  Not part of the
+// captured evaluation graphs: two launches straight on the context stream.
+int gprx_batch_loo(gprx_batch* b, double* mu, double* var, double* logp_i, double* logp, int* status) {
+  if (!b) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!b->factored) return set_err(c, GPRX_NOT_READY, "leave-one-out before a successful factorisation");
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const DevBatch& db = b->db;
+  const size_t rows = (size_t)db.B * db.Npad;
+  char* base = nullptr;
+  int rc = ctx_scratch(c, (4 * rows + db.B) * sizeof(double), &base);
+  if (rc) return rc;
+  double* kinv = (double*)base;
+  double *d_mu = kinv + rows, *d_var = d_mu + rows, *d_lp = d_var + rows, *d_logp = d_lp + rows;
+  const double B = db.B, N = db.N, tri = N * (N + 1.0) / 2.0;
+  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, kinv, c->stream); });
+  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
+        [&] { gprx::launch_loo_final(db, kinv, d_mu, d_var, d_lp, d_logp, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  const size_t w = (size_t)db.N * sizeof(double), p = (size_t)db.Npad * sizeof(double);
+  if (mu) HIPCHK(c, hipMemcpy2DAsync(mu, w, d_mu, p, w, db.B, hipMemcpyDeviceToHost, c->stream));
+  if (var) HIPCHK(c, hipMemcpy2DAsync(var, w, d_var, p, w, db.B, hipMemcpyDeviceToHost, c->stream));
+  if (logp_i) HIPCHK(c, hipMemcpy2DAsync(logp_i, w, d_lp, p, w, db.B, hipMemcpyDeviceToHost, c->stream));
+  if (logp) HIPCHK(c, hipMemcpyAsync(logp, d_logp, (size_t)db.B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  // h_status: the evaluation that factorised the batch (gprx_batch_alpha); k_loo_final wrote the
+  // NaN rows of a failed slot from the same status on the device
+  int first = GPRX_OK;
+  for (int s = 0; s < db.B; ++s) {
+    const int st = b->h_status[s];
+    if (status) status[s] = st;
+    if (st != GPRX_OK && first == GPRX_OK) first = st;
+  }
+  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_loo: ") + gprx_status_string(first));
+  return first;
+}
+
+int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp) {
+  if (!gp) return GPRX_INVALID_ARGUMENT;
+  return gprx_batch_loo(gp->batch, mu, var, nullptr, logp, nullptr);
+}
+
 // The ngroups x G GPs of a rollout (entry point fn), gathered from batch slots of this context that
 // have input dimension d (dwhat: how the message names it), are factorised and passed their last
 // evaluation; the trajectories' groups range-checked.  *np: the training points a trajectory step

@@ -411,6 +411,9 @@ void launch_pred_cov(const DevBatch& b, const double* VT, double* Sig, hipStream
 void launch_cov_chol(const DevBatch& b, const double* Sig, double* F, size_t fs, double* jit, int* st, hipStream_t s);
 void launch_cov_sample(const DevBatch& b, const double* F, size_t fs, const double* Z, size_t zs, double* smp, size_t ss,
                        int S, const int* st, hipStream_t s);
+// leave-one-out predictions (gprx_loo.h).  kinv, mu, var, lp: B x Npad; logp: B
+void launch_loo_diag(const DevBatch& b, double* kinv, hipStream_t s);
+void launch_loo_final(const DevBatch& b, const double* kinv, double* mu, double* var, double* lp, double* logp, hipStream_t s);
 void launch_lbfgs(const LbArgs& a, const DevBatch& db, int init, hipStream_t s);  // gprx_lbfgs.hip
 void launch_lbfgs_final(const LbArgs& a, const DevBatch& db, hipStream_t s);
 

@@ -1146,3 +1146,5 @@ void launch_pred_final(const DevBatch& b, hipStream_t s) {
 
 // Last: the joint-covariance kernels follow every evaluation kernel in the code object.
 #include "gprx_predcov.h"
+// ... and the leave-one-out kernels.
+#include "gprx_loo.h"

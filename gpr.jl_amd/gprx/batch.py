@@ -311,6 +311,19 @@ class GPBatch:
         L.check(L.lib.gprx_batch_alpha(self.h, L.dptr(out)), self.ctx.h)
         return out
 
+    def loo(self, raise_on_error: bool = False):
+        """Leave-one-out predictions from the last factorisation [ext predict_LOO(gp), logp_LOO(gp)]:
+        dict(mu[B,N], var[B,N], logp_i[B,N], logp[B], status[B]).  mu is in the space of the targets
+        given to set_train (y - mean(X)); var includes the noise variance.  NaN rows for the slots
+        that failed in that evaluation; their status raises only with raise_on_error (as run)."""
+        mu, var, lpi = (np.empty((self.B, self.N)) for _ in range(3))
+        lp = np.empty(self.B)
+        st = np.empty(self.B, dtype=np.int32)
+        rc = L.lib.gprx_batch_loo(self.h, L.dptr(mu), L.dptr(var), L.dptr(lpi), L.dptr(lp), L.iptr(st))
+        if rc not in (L.OK, L.NOT_POSITIVE_DEFINITE, L.INVALID_ARGUMENT) or (raise_on_error and rc != L.OK):
+            L.check(rc, self.ctx.h)
+        return dict(mu=mu, var=var, logp_i=lpi, logp=lp, status=st)
+
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):  # a closed context already synchronised its stream

@@ -233,6 +233,17 @@ class GPE:
         smp, _ = self._batch.sample(Z, raise_on_error=True)
         return (smp[0] + self.mean.mean(xs)[None, :]).T.copy()
 
+    def predict_LOO(self):
+        """(μ_i, σ²_i) of every training point predicted from the other N - 1 [ext predict_LOO(gp)],
+        from the last factorisation: the prior mean at x is added back here, σ² is in y-space (it
+        includes the noise)."""
+        r = self._batch.loo(raise_on_error=True)
+        return r["mu"][0] + self._mu, r["var"][0].copy()
+
+    def logp_LOO(self) -> float:
+        """Sum of the leave-one-out log predictive densities [ext logp_LOO(gp)]."""
+        return float(self._batch.loo(raise_on_error=True)["logp"][0])
+
     def predict_y_mean(self, xs):
         """predict_y(gp, obs)[1] without the variance: the rollout call of
         examples/utils/predictdynamics.jl:13 (uses the mean only); skips the O(N^2 M) variance."""
@@ -261,3 +272,11 @@ def predict_f(gp: GPE, xs, full_cov: bool = False):
 
 def rand(gp: GPE, xs, n: int = 1, rng=None):
     return gp.rand(xs, n, rng)
+
+
+def predict_LOO(gp: GPE):
+    return gp.predict_LOO()
+
+
+def logp_LOO(gp: GPE) -> float:
+    return gp.logp_LOO()

@@ -101,9 +101,11 @@ def local_trials(exp: str, N: int, trial_ids, testsamples: int) -> list[dict]:
 
 
 def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
-                     max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False) -> dict:
+                     max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
+                     loo: bool = False) -> dict:
     """One (experiment, N) of parallelsearch for this rank's trials (sweep.run_group on the
-    search's inputs).  Adds the per-trial raw start params (n_local, d+1)."""
+    search's inputs).  Adds the per-trial raw start params (n_local, d+1).  loo: also loo_logp
+    (n_local, G), logp_LOO of every GP at its minimiser (sweep.run_group); recorded, not used."""
     from .sweep import run_group
 
     mech, coords = split(exp)
@@ -111,7 +113,7 @@ def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, s
     if not trials:
         return {}
     r = run_group(mech, N, "max" if coords == "MAX" else "min", [t["trial"] for t in trials], ctx, testsamples,
-                  simsteps, max_evals, time_limit, keep=keep, trials=trials)
+                  simsteps, max_evals, time_limit, keep=keep, trials=trials, loo=loo)
     r["params"] = np.stack([t["params"] for t in trials])
     return r
 
@@ -137,10 +139,11 @@ def _dist():
 
 
 def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
-        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None) -> dict:
+        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None, loo: bool = False) -> dict:
     """hyperparameter.jl's loop (N outer, experiments inner).  Every rank runs its trials of every
     group; rank 0 returns the gathered params_final checkpoint (other ranks None).  Without an
-    initialised process group: one rank."""
+    initialised process group: one rank.  loo: every entry of the checkpoint also lists loo_logp, one
+    row of G values per kept trial; createconfig still selects by kstep_mse."""
     from .batch import Context
 
     dist = _dist()
@@ -156,7 +159,8 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
         for exp in experiments:
             mech, coords = split(exp)
             d = 13 * data.NBODIES[mech] if coords == "MAX" else 2 * len(data.MIN_COORDS[mech])
-            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit)
+            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit, loo=loo)
+            G = len(data.VW_INDICES[mech]) if coords == "MAX" else len(data.MIN_COORDS[mech])
             n = len(mine)
             nb = int(r.get("batches", 1 if r else 0))
             local = {"kstep_mse": r.get("kstep_mse", np.zeros(0)),
@@ -164,10 +168,13 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
                      "params": r.get("params", np.zeros((0, d + 1))),
                      "t": np.full(n, r.get("t_opt", 0.0) + r.get("t_eval", 0.0))}
             width = {"params": d + 1}
+            keys = ("kstep_mse", "failed", "params", "t")
+            if loo:
+                local["loo_logp"], width["loo_logp"], keys = r.get("loo_logp", np.zeros((0, G))), G, keys + ("loo_logp",)
             local = {k: np.asarray(v, dtype=np.float64).reshape(n, width.get(k, 1)) for k, v in local.items()}
             if dist:
                 g = shard.gather_results(local, n_trials, lambda q: shard.shard_trials(n_trials, q, world), 0,
-                                         keys=("kstep_mse", "failed", "params", "t"))
+                                         keys=keys)
             else:
                 g = local
             key = f"{exp}{N}"
@@ -177,6 +184,8 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
                                           "params": [[float(x) for x in row] for row in g["params"][keep]],
                                           "kstep_mse": [float(v) for v in g["kstep_mse"][keep, 0]],
                                           "dropped": int((~keep).sum())}
+                if loo:
+                    results["params"][key]["loo_logp"] = [[float(x) for x in row] for row in g["loo_logp"][keep]]
                 timing[key] = {"seconds_max_rank": float(np.max(g["t"][:, 0])) if n_trials else 0.0,
                                "device_batches_rank0": nb,
                                "gp_fits": n_trials * (len(data.VW_INDICES[mech]) if coords == "MAX"
@@ -202,6 +211,7 @@ def main(argv=None):
     ap.add_argument("--simsteps", type=int, default=20)
     ap.add_argument("--max-evals", type=int, default=30, help="evaluation budget per GP (<= 0: none)")
     ap.add_argument("--time-limit", type=float, default=float("nan"), help="seconds per group call (NaN: none)")
+    ap.add_argument("--loo", action="store_true", help="record logp_LOO of every GP at its minimiser (loo_logp)")
     ap.add_argument("--out", default="gpurun_out/params_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -218,7 +228,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = run([e for e in a.experiments.split(",") if e], [int(s) for s in a.sizes.split(",") if s], a.trials,
               a.testsamples, a.simsteps, a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True))
+              log=lambda s: print(s, flush=True), loo=a.loo)
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

@@ -137,7 +137,8 @@ def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, c
 
 def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
               max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
-              trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise", dataset=None) -> dict:
+              trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise", dataset=None,
+              loo: bool = False) -> dict:
     """One (mechanism, N, variant) group for this rank's trials: device optimise of every GP,
     then the variant's evaluation.  Returns per-trial arrays (n_local, ...) and timings.
     trials: prebuilt local_trials-shaped inputs (the hyper-parameter search's), else noise.jl's.
@@ -147,7 +148,10 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     md_rollout: how the md_* variants roll out -- "stepwise" (a host loop of three device calls per
     step, gprx.mdynamics.rollout_max / rollout_min) or "device" (every step in one launch,
     gprx.mdynamics.rollout_max_device / rollout_min_device).
-    dataset: take the trials from simulated datasets (local_trials) and the truth from their sfuture."""
+    dataset: take the trials from simulated datasets (local_trials) and the truth from their sfuture.
+    loo: also return loo_logp (n_local, G), logp_LOO of every GP at its minimiser (GPBatch.loo right
+    after the optimiser's refit, in every device batch; NaN where the refit failed).  Recorded only:
+    nothing selects by it.  Off: the result is what it was, key for key."""
     if md_rollout not in MD_ROLLOUTS:
         raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")
     if trials is None:
@@ -161,7 +165,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     parts = []
     for lo, hi, nd in plan:
         rb = shard.RankBatch(trials[lo:hi], ctx=ctx, dev_trials=nd)
-        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout)
+        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout, loo)
         if keep:
             part.update(rb=rb, trials=trials)
         else:
@@ -170,13 +174,13 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     if len(parts) == 1:
         return parts[0]
     out = {k: np.concatenate([p[k] for p in parts]) for k in ("kstep_mse", "projectionerror", "failed", "mll", "theta",
-                                                              "status", "f_calls")}
+                                                              "status", "f_calls") + (("loo_logp",) if loo else ())}
     out.update(rounds=sum(p["rounds"] for p in parts), t_opt=sum(p["t_opt"] for p in parts),
                t_eval=sum(p["t_eval"] for p in parts), slots=sum(p["slots"] for p in parts), batches=len(parts))
     return out
 
 
-def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise") -> dict:
+def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise", loo=False) -> dict:
     """run_group's work for the trials of one device batch rb."""
     from .optim import LBFGS, Options
 
@@ -186,6 +190,8 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
     opt = rb.optimize(th0, LBFGS(), Options(max_evals=max_evals, time_limit=time_limit))
     t_opt = time.perf_counter() - t0
     G = rb.G
+    # the batch is factorised at the minimisers (rb.optimize's closing evaluation)
+    loo_logp = np.where(opt["status"] == 0, rb._shape(rb.batch.loo()["logp"]), np.nan) if loo else None
     ok_gp = opt["status"] == 0  # (n, G)
     ok_gp &= np.array([[not t.get("vi_failed", False)] for t in trials])  # MeanDynamics mean failed: dropped
     err = np.full(n, math.inf)
@@ -255,9 +261,12 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
                 err[i] = data.position_mse(truth, pred)
                 failed[i] = False
     t_eval = time.perf_counter() - t1
-    return dict(kstep_mse=err, projectionerror=perr, failed=failed, mll=opt["mll"], theta=opt["theta"],
-                status=opt["status"], f_calls=opt["f_calls"], rounds=opt["rounds"], t_opt=t_opt, t_eval=t_eval,
-                slots=n * G, batches=1)
+    out = dict(kstep_mse=err, projectionerror=perr, failed=failed, mll=opt["mll"], theta=opt["theta"],
+               status=opt["status"], f_calls=opt["f_calls"], rounds=opt["rounds"], t_opt=t_opt, t_eval=t_eval,
+               slots=n * G, batches=1)
+    if loo:
+        out["loo_logp"] = loo_logp
+    return out
 
 
 def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int = 20, ctx=None, dataset=None,

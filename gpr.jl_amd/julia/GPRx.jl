@@ -10,6 +10,7 @@ experiment scripts (examples/noise.jl, examples/hyperparameter.jl) stay textuall
     predict_y(gp, x*)                     -> gprx_gp_predict                 (predictdynamics.jl:13)
     predict_f(gp, x*; full_cov=true)      -> gprx_gp_predict_cov
     rand(gp, x*, n)                       -> gprx_gp_sample (randn on the Julia side)
+    predict_LOO(gp), logp_LOO(gp)         -> gprx_gp_loo
 
 plus `GPRx.optimize_all!(gps)`: the loop `for gp in gps; optimize!(gp, LBFGS(linesearch =
 BackTracking(order=2)), Optim.Options(time_limit=10.)); end` of CPnoise.jl:37-43 as ONE
@@ -170,6 +171,24 @@ function Random.rand(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, x::AbstractMatrix, n::
     return out .+ GaussianProcesses.mean(gp.mean, xs)
 end
 Random.rand(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, x::AbstractMatrix) = vec(rand(gp, x, 1))
+
+# predict_LOO(gp), logp_LOO(gp) (GaussianProcesses crossvalidation.jl): the leave-one-out mean and
+# variance at every training point and the summed log predictive density, from the device
+# factorisation of the last evaluation (gprx_gp_loo: R&W 5.10-5.12 over diag(K^-1) and alpha).  The
+# prior mean at the training inputs is added back here; the variance includes the noise.
+function GaussianProcesses.predict_LOO(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd})
+    N = length(gp.y)
+    mu, var = zeros(N), zeros(N)
+    check(ccall((:gprx_gp_loo, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                handle(gp).ptr, mu, var, C_NULL), gp)
+    return mu .+ GaussianProcesses.mean(gp.mean, Matrix{Float64}(gp.x)), var
+end
+function GaussianProcesses.logp_LOO(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd})
+    lp = Ref{Float64}(0.0)
+    check(ccall((:gprx_gp_loo, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                handle(gp).ptr, C_NULL, C_NULL, lp), gp)
+    return lp[]
+end
 
 # predictdynamicsmin (examples/utils/predictdynamics.jl:30-102) for all test observations of one
 # trial in one device launch.  `gps` must be MeanZero GPEs evaluated on this thread's context (the

@@ -15,6 +15,7 @@
  *   gprx_gp_predict    predict_f / predict_y(gp, x*)  examples/utils/predictdynamics.jl:13
  *   gprx_gp_predict_cov, gprx_gp_sample   [ext] predict_f(gp, x; full_cov=true), rand(gp, x, n): on
  *                      every GPE (CPnoise.jl:40); the reference's scripts use the mean only
+ *   gprx_gp_loo / gprx_batch_loo   [ext] predict_LOO(gp), logp_LOO(gp) (crossvalidation.jl), on every GPE
  *   gprx_rollout_min   predictdynamicsmin             examples/utils/predictdynamics.jl:30-102
  *   gprx_batch_*       the G per-output GPs of a trial (CPnoise.jl:37-43) and the trial loop
  *                      (examples/parallel/core.jl:28) evaluated as one device batch
@@ -195,6 +196,27 @@ int gprx_batch_sample(gprx_batch* batch, const double* Z, int S, int64_t z_slot_
  * refuses, or Mpad^2 * 8 beyond the addressing range.                                            */
 int gprx_batch_cov_bytes(int B, int N, int M_max, uint64_t* bytes);
 
+/* ---- leave-one-out predictions -------------------------------------------------------------- */
+/* [ext] predict_LOO(gp) and logp_LOO(gp) of GaussianProcesses 0.12.4 (crossvalidation.jl), which
+ * every GPE the reference builds carries (examples/maximal_coordinates/CPnoise.jl:40): the
+ * predictive mean and variance at each training point from the other N - 1, its log predictive
+ * density and their sum, from the factorisation of the last evaluation (no refit).  With
+ * kinv_i = [K^-1]_ii = sum_{k >= i} (L^-1)_ki^2 and alpha = K^-1 y (Rasmussen & Williams 5.10-5.12):
+ *   var_i    = 1 / kinv_i                  (y-space: K carries exp(2 log sn) + eps on its diagonal)
+ *   mu_i     = y_i - alpha_i / kinv_i      (in the space of the targets given to set_train, y - mean(X))
+ *   logp_i   = 0.5 log(kinv_i) - 0.5 alpha_i^2 / kinv_i - 0.5 log(2 pi),   logp[b] = sum_i logp_i
+ * GaussianProcesses' source was not available to compare against: the formulas are R&W's and the
+ * convention (y-space variance, the prior mean left to the host) is gprx's own.
+ * Host outputs, any may be NULL: mu[B*N], var[B*N], logp_i[B*N], logp[B], status[B] (that
+ * evaluation's per-slot status).  GPRX_NOT_READY before a successful factorisation;
+ * GPRX_INVALID_ARGUMENT for a NULL batch.  A slot whose status in that evaluation was not GPRX_OK
+ * gets NaN in its rows and its logp (as gprx_batch_alpha); the other slots are unaffected.  Returns
+ * GPRX_OK or the first failing slot's status, as gprx_batch_run.  The results are bitwise
+ * reproducible and do not depend on B or on the slot's place in the batch.  The workspace
+ * (8 B (4 Npad + 1) bytes) comes from the context's scratch buffer; gprx_batch_bytes is unchanged.
+ * The launches go straight on the context stream (stats "loo_diag", "loo_final").                */
+int gprx_batch_loo(gprx_batch* batch, double* mu, double* var, double* logp_i, double* logp, int* status);
+
 /* ---- hyper-parameter optimisation on the device ------------------------------------------- */
 /* GaussianProcesses.optimize!(gp, LBFGS(linesearch=BackTracking(order=2)), Optim.Options(...))
  * (examples/maximal_coordinates/CPnoise.jl:41 and its 15 siblings) for every slot of a batch:
@@ -272,6 +294,9 @@ int gprx_gp_predict(gprx_gp* gp, const double* Xs, int M, double* mu_f, double* 
  * gprx_batch_sample (whose jitter rule is gprx's own).                                          */
 int gprx_gp_predict_cov(gprx_gp* gp, const double* Xs, int M, double* mu, double* cov);
 int gprx_gp_sample(gprx_gp* gp, const double* Xs, int M, const double* Z, int S, double* samples, double* jitter);
+/* [ext] predict_LOO(gp): mu[N], var[N]; logp_LOO(gp): logp[1]; any may be NULL (gprx_batch_loo on
+ * the batch of one, at the factorisation of the last lml call).                                  */
+int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp);
 
 /* the single GP's underlying batch of one (slot 0), e.g. for gprx_rollout_min              */
 gprx_batch* gprx_gp_batch(gprx_gp* gp);
