@@ -1376,6 +1376,63 @@ int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp) {
   return gprx_batch_loo(gp->batch, mu, var, nullptr, logp, nullptr);
 }
 
+// ---- gradient of the leave-one-out log predictive probability (gprx_loograd.h) ---------------------
+// Workspace in the context scratch: gprx_batch_loo's (kinv, mu, var, lp, logp), beta (B x Npad), the
+// beta partials (B x nt x Npad), the unit partials (B x ngu x gps) and the result rows (B x (d + 3)).
+// P = K^-1 diag(sqrt c) goes to Lw, which only the factorisation reads and every evaluation rewrites.
+// Not part of the captured evaluation graphs: six launches straight on the context stream.
+int gprx_batch_loo_grad(gprx_batch* b, double* logp, double* grad, int* status) {
+  if (!b) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!b->factored) return set_err(c, GPRX_NOT_READY, "leave-one-out gradient before a successful factorisation");
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const DevBatch& db = b->db;
+  const int d = db.d;
+  const size_t rows = (size_t)db.B * db.Npad;
+  const size_t n_bp = rows * db.nt, n_gp = (size_t)db.B * db.ngu * db.gps, n_out = (size_t)db.B * (d + 3);
+  char* base = nullptr;
+  int rc = ctx_scratch(c, (5 * rows + db.B + n_bp + n_gp + n_out) * sizeof(double), &base);
+  if (rc) return rc;
+  double* kinv = (double*)base;
+  double *d_mu = kinv + rows, *d_var = d_mu + rows, *d_lp = d_var + rows, *d_beta = d_lp + rows;
+  double *d_bp = d_beta + rows, *d_gp = d_bp + n_bp, *d_out = d_gp + n_gp, *d_logp = d_out + n_out;
+  const double B = db.B, N = db.N, Np = db.Npad, tri = N * (N + 1.0) / 2.0;
+  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, kinv, c->stream); });
+  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
+        [&] { gprx::launch_loo_final(db, kinv, d_mu, d_var, d_lp, d_logp, c->stream); });
+  timed(c, c->stream, "loo_kinv", B * (Np * Np * Np / 3.0 + 4.0 * Np * Np), B * 8.0 * (1.5 * Np * Np + 2.0 * db.nt * Np),
+        [&] { gprx::launch_loo_kinv(db, kinv, d_bp, c->stream); });
+  timed(c, c->stream, "loo_beta", B * db.nt * Np, B * 8.0 * (db.nt + 1.0) * Np, [&] { gprx::launch_loo_beta(db, d_bp, d_beta, c->stream); });
+  timed(c, c->stream, "loo_grad", B * (Np * Np * Np + Np * Np * db.da + 6.0 * Np * Np),
+        B * 8.0 * (1.5 * Np * Np + Np * db.da), [&] { gprx::launch_loo_grad(db, d_beta, d_gp, c->stream); });
+  timed(c, c->stream, "loo_grad_final", B * (double)db.ngu * db.gps, B * 8.0 * ((double)db.ngu * db.gps + d + 3),
+        [&] { gprx::launch_loo_grad_final(db, d_gp, d_logp, d_out, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  const size_t ro = (size_t)(d + 3) * sizeof(double);
+  if (logp) HIPCHK(c, hipMemcpy2DAsync(logp, sizeof(double), d_out, ro, sizeof(double), db.B, hipMemcpyDeviceToHost, c->stream));
+  if (grad)
+    HIPCHK(c, hipMemcpy2DAsync(grad, (size_t)(d + 2) * sizeof(double), d_out + 1, ro, (size_t)(d + 2) * sizeof(double), db.B,
+                               hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  // h_status: the evaluation that factorised the batch; k_loo_grad_final wrote the NaN rows of a
+  // failed slot from the same status on the device
+  int first = GPRX_OK;
+  for (int s = 0; s < db.B; ++s) {
+    const int st = b->h_status[s];
+    if (status) status[s] = st;
+    if (st != GPRX_OK && first == GPRX_OK) first = st;
+  }
+  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_loo_grad: ") + gprx_status_string(first));
+  return first;
+}
+
+int gprx_gp_loo_grad(gprx_gp* gp, double* logp, double* grad) {
+  if (!gp) return GPRX_INVALID_ARGUMENT;
+  return gprx_batch_loo_grad(gp->batch, logp, grad, nullptr);
+}
+
 // The ngroups x G GPs of a rollout (entry point fn), gathered from batch slots of this context that
 // have input dimension d (dwhat: how the message names it), are factorised and passed their last
 // evaluation; the trajectories' groups range-checked.  *np: the training points a trajectory step

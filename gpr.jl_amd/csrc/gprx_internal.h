@@ -414,6 +414,12 @@ void launch_cov_sample(const DevBatch& b, const double* F, size_t fs, const doub
 // leave-one-out predictions (gprx_loo.h).  kinv, mu, var, lp: B x Npad; logp: B
 void launch_loo_diag(const DevBatch& b, double* kinv, hipStream_t s);
 void launch_loo_final(const DevBatch& b, const double* kinv, double* mu, double* var, double* lp, double* logp, hipStream_t s);
+// gradient of the leave-one-out log predictive probability (gprx_loograd.h).  bpart: B x nt x Npad;
+// beta: B x Npad; gpart: B x ngu x gps; out: B x (d + 3) = [logp, grad[d + 2]]
+void launch_loo_kinv(const DevBatch& b, const double* kinv, double* bpart, hipStream_t s);
+void launch_loo_beta(const DevBatch& b, const double* bpart, double* beta, hipStream_t s);
+void launch_loo_grad(const DevBatch& b, const double* beta, double* gpart, hipStream_t s);
+void launch_loo_grad_final(const DevBatch& b, const double* gpart, const double* logp, double* out, hipStream_t s);
 void launch_lbfgs(const LbArgs& a, const DevBatch& db, int init, hipStream_t s);  // gprx_lbfgs.hip
 void launch_lbfgs_final(const LbArgs& a, const DevBatch& db, hipStream_t s);
 

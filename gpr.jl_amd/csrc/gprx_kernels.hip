@@ -1062,6 +1062,7 @@ static size_t cross_lds(int d) { return (size_t)(2 * d * CS + 2 * DMAX + 4 + 4 *
 // gprx_ctx_create (std::call_once per device index) before any launch, so concurrent contexts on
 // other threads never launch a kernel whose attribute is not yet set.
 static void set_predcov_attributes();  // gprx_predcov.h
+static void set_loograd_attributes();  // gprx_loograd.h
 void set_kernel_attributes() {
   for (const void* f : {(const void*)k_gram<0>, (const void*)k_gram<1>})
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds(DMAX));
@@ -1074,6 +1075,7 @@ void set_kernel_attributes() {
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)linv21_lds_bytes());
   set_lbfgs_attributes();
   set_predcov_attributes();
+  set_loograd_attributes();
 }
 
 void launch_gram(const DevBatch& b, hipStream_t s) {
@@ -1148,3 +1150,5 @@ void launch_pred_final(const DevBatch& b, hipStream_t s) {
 #include "gprx_predcov.h"
 // ... and the leave-one-out kernels.
 #include "gprx_loo.h"
+// ... and the gradient of their log predictive probability.
+#include "gprx_loograd.h"

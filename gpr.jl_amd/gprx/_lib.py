@@ -83,6 +83,7 @@ SIGNATURES = {
     "gprx_batch_sample": (C.c_int, [_vp, _dp, C.c_int, C.c_int64, _dp, _dp, _ip]),
     "gprx_batch_cov_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "gprx_batch_loo": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),
+    "gprx_batch_loo_grad": (C.c_int, [_vp, _dp, _dp, _ip]),
     "gprx_opt_defaults": (None, [C.POINTER(OptOptions)]),
     "gprx_batch_optimize": (C.c_int, [_vp, _dp, C.POINTER(OptOptions), _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "gprx_batch_set_opt_trace": (C.c_int, [_vp, _dp, C.c_int, C.c_int64]),
@@ -94,6 +95,7 @@ SIGNATURES = {
     "gprx_gp_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gprx_gp_sample": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "gprx_gp_loo": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "gprx_gp_loo_grad": (C.c_int, [_vp, _dp, _dp]),
     "gprx_gp_batch": (_vp, [_vp]),
     "gprx_rollout_min": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(_vp), _ip, C.c_int,
                                    _ip, _dp, _dp]),
@@ -155,7 +157,8 @@ def _load():
 # the library's sources, in the order gpr.jl_amd/Makefile hashes them (SRC then HDR)
 BUILD_SOURCES = ["csrc/gprx_kernels.hip", "csrc/gprx_lbfgs.hip", "csrc/gprx_projection.hip", "csrc/gprx_api.hip",
                  "csrc/gprx_internal.h", "csrc/gprx_device.h", "csrc/gprx_cores.h", "csrc/gprx_stamps.h",
-                 "csrc/gprx_gemm.h", "csrc/gprx_factor.h", "csrc/gprx_predcov.h", "csrc/gprx_loo.h", "../include/gprx.h"]
+                 "csrc/gprx_gemm.h", "csrc/gprx_factor.h", "csrc/gprx_predcov.h", "csrc/gprx_loo.h", "csrc/gprx_loograd.h",
+                 "../include/gprx.h"]
 
 
 def source_build_id():

@@ -324,6 +324,19 @@ class GPBatch:
             L.check(rc, self.ctx.h)
         return dict(mu=mu, var=var, logp_i=lpi, logp=lp, status=st)
 
+    def loo_grad(self, raise_on_error: bool = False):
+        """Gradient of the leave-one-out log predictive probability at the last factorisation and its
+        theta [ext, recalled: dlogpdθ_LOO(gp)]: dict(logp[B], grad[B, d+2], status[B]), grad in the
+        order of theta, [log σn, log ℓ_1..d, log σf].  logp is loo()'s, bit for bit.  NaN rows for the
+        slots that failed in that evaluation; their status raises only with raise_on_error (as run)."""
+        lp = np.empty(self.B)
+        gr = np.empty((self.B, self.d + 2))
+        st = np.empty(self.B, dtype=np.int32)
+        rc = L.lib.gprx_batch_loo_grad(self.h, L.dptr(lp), L.dptr(gr), L.iptr(st))
+        if rc not in (L.OK, L.NOT_POSITIVE_DEFINITE, L.INVALID_ARGUMENT) or (raise_on_error and rc != L.OK):
+            L.check(rc, self.ctx.h)
+        return dict(logp=lp, grad=gr, status=st)
+
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):  # a closed context already synchronised its stream

@@ -244,6 +244,11 @@ class GPE:
         """Sum of the leave-one-out log predictive densities [ext logp_LOO(gp)]."""
         return float(self._batch.loo(raise_on_error=True)["logp"][0])
 
+    def dlogpdtheta_LOO(self) -> np.ndarray:
+        """Gradient of logp_LOO with respect to the hyper-parameters, in the order of get_params
+        [ext, recalled: dlogpdθ_LOO(gp)]; the prior mean has no parameters here."""
+        return self._batch.loo_grad(raise_on_error=True)["grad"][0].copy()
+
     def predict_y_mean(self, xs):
         """predict_y(gp, obs)[1] without the variance: the rollout call of
         examples/utils/predictdynamics.jl:13 (uses the mean only); skips the O(N^2 M) variance."""
@@ -280,3 +285,7 @@ def predict_LOO(gp: GPE):
 
 def logp_LOO(gp: GPE) -> float:
     return gp.logp_LOO()
+
+
+def dlogpdtheta_LOO(gp: GPE) -> np.ndarray:
+    return gp.dlogpdtheta_LOO()

@@ -316,7 +316,7 @@ def optimize(gp, method: LBFGS | None = None, options: Options | None = None) ->
 
 
 def optimize_batch(batch, theta0, method: LBFGS | None = None, options: Options | None = None,
-                   trace: list | None = None):
+                   trace: list | None = None, objective: str = "mll"):
     """One LBFGS run per slot of a GPBatch (the per-output GPs of CPnoise.jl:37-43 and the trials
     of examples/parallel/core.jl:28), in lock-step: every round answers all pending requests with
     ONE device evaluation of the whole batch (value + gradient for every slot).  Each slot follows
@@ -326,7 +326,13 @@ def optimize_batch(batch, theta0, method: LBFGS | None = None, options: Options 
     slots answer +Inf as in `optimize`.
     trace: a list that receives one (B, 2n+2) array per round, rows [active, theta(n), mll,
     dmll(n)] -- the layout of GPBatch.optimize's `last_opt_trace` (gprx_batch_set_opt_trace).
+    objective: "mll" (the default: minimise -mll, the path above) or "loo": minimise -logp_LOO, every
+    round answered by batch.run(th, grad=False) followed by batch.loo_grad() (the leave-one-out log
+    predictive probability and its gradient at that factorisation; the trace rows then hold logp and
+    its gradient).  Failed slots answer +Inf either way.
     Returns (results, rounds)."""
+    if objective not in ("mll", "loo"):
+        raise ValueError(f"objective must be 'mll' or 'loo', not {objective!r}")
     theta0 = np.asarray(theta0, dtype=np.float64)
     B, npar = theta0.shape
     gens = [lbfgs_steps(theta0[s], method, options) for s in range(B)]
@@ -352,7 +358,12 @@ def optimize_batch(batch, theta0, method: LBFGS | None = None, options: Options 
             th[s] = x if np.all(np.isfinite(x)) else theta0[s]
         if todo:
             rounds += 1
-            r = batch.run(th, grad=True, predict=False)
+            if objective == "loo":
+                st = batch.run(th, grad=False, predict=False)["status"]
+                lg = batch.loo_grad()
+                r = dict(status=np.where(np.asarray(st) != 0, st, lg["status"]), mll=lg["logp"], grad=lg["grad"])
+            else:
+                r = batch.run(th, grad=True, predict=False)
             if trace is not None:
                 act = np.zeros((B, 1))
                 act[todo] = 1.0

@@ -102,10 +102,12 @@ def local_trials(exp: str, N: int, trial_ids, testsamples: int) -> list[dict]:
 
 def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
                      max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
-                     loo: bool = False) -> dict:
+                     loo: bool = False, objective: str = "mll") -> dict:
     """One (experiment, N) of parallelsearch for this rank's trials (sweep.run_group on the
     search's inputs).  Adds the per-trial raw start params (n_local, d+1).  loo: also loo_logp
-    (n_local, G), logp_LOO of every GP at its minimiser (sweep.run_group); recorded, not used."""
+    (n_local, G), logp_LOO of every GP at its minimiser (sweep.run_group); recorded, not used.
+    objective: "mll" (the default, unchanged) or "loo": the GPs minimise -logp_LOO on the host loop
+    (optim.optimize_batch over GPBatch.loo_grad); the result's keys are the same."""
     from .sweep import run_group
 
     mech, coords = split(exp)
@@ -113,7 +115,7 @@ def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, s
     if not trials:
         return {}
     r = run_group(mech, N, "max" if coords == "MAX" else "min", [t["trial"] for t in trials], ctx, testsamples,
-                  simsteps, max_evals, time_limit, keep=keep, trials=trials, loo=loo)
+                  simsteps, max_evals, time_limit, keep=keep, trials=trials, loo=loo, objective=objective)
     r["params"] = np.stack([t["params"] for t in trials])
     return r
 
@@ -139,7 +141,8 @@ def _dist():
 
 
 def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
-        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None, loo: bool = False) -> dict:
+        max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None, loo: bool = False,
+        objective: str = "mll") -> dict:
     """hyperparameter.jl's loop (N outer, experiments inner).  Every rank runs its trials of every
     group; rank 0 returns the gathered params_final checkpoint (other ranks None).  Without an
     initialised process group: one rank.  loo: every entry of the checkpoint also lists loo_logp, one
@@ -159,7 +162,7 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
         for exp in experiments:
             mech, coords = split(exp)
             d = 13 * data.NBODIES[mech] if coords == "MAX" else 2 * len(data.MIN_COORDS[mech])
-            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit, loo=loo)
+            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit, loo=loo, objective=objective)
             G = len(data.VW_INDICES[mech]) if coords == "MAX" else len(data.MIN_COORDS[mech])
             n = len(mine)
             nb = int(r.get("batches", 1 if r else 0))
@@ -212,6 +215,8 @@ def main(argv=None):
     ap.add_argument("--max-evals", type=int, default=30, help="evaluation budget per GP (<= 0: none)")
     ap.add_argument("--time-limit", type=float, default=float("nan"), help="seconds per group call (NaN: none)")
     ap.add_argument("--loo", action="store_true", help="record logp_LOO of every GP at its minimiser (loo_logp)")
+    ap.add_argument("--objective", choices=("mll", "loo"), default="mll",
+                    help="what every GP's optimiser minimises: -mll (device LBFGS) or -logp_LOO (host loop)")
     ap.add_argument("--out", default="gpurun_out/params_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -228,7 +233,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = run([e for e in a.experiments.split(",") if e], [int(s) for s in a.sizes.split(",") if s], a.trials,
               a.testsamples, a.simsteps, a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True), loo=a.loo)
+              log=lambda s: print(s, flush=True), loo=a.loo, objective=a.objective)
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

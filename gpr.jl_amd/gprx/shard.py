@@ -267,15 +267,22 @@ class RankBatch:
         r = self.batch.run(self._rows(theta), grad=grad, predict=pred, variance=variance)
         return {k: self._shape(v) for k, v in r.items() if v is not None}
 
-    def optimize(self, theta0, method=None, options=None) -> dict:
+    def optimize(self, theta0, method=None, options=None, objective: str = "mll") -> dict:
         """optimize! for every GP of every local trial in one device call (k_lbfgs, lock-step),
         then one evaluation at the minimisers (update_target!, with prediction when the trials
         have test points).  A slot whose refit fails is reported in `status` (the reference's
-        experiment throws and the trial is dropped, core.jl:41-46), the others stay valid."""
+        experiment throws and the trial is dropped, core.jl:41-46), the others stay valid.
+        objective="loo": minimise -logp_LOO instead, on the host loop (optim.optimize_batch: the device
+        state machine k_lbfgs knows the marginal likelihood only)."""
         if self.batch is None:
             return {}
         th0 = self._rows(theta0)
-        res, rounds = self.batch.optimize(th0, method, options, refit=False)
+        if objective == "mll":
+            res, rounds = self.batch.optimize(th0, method, options, refit=False)
+        else:
+            from .optim import optimize_batch
+
+            res, rounds = optimize_batch(self.batch, th0, method, options, objective=objective)
         thmin = np.stack([r.minimizer for r in res])
         ok = np.all(np.isfinite(thmin), axis=1)
         # a non-finite minimiser (NaN-gradient stop) is evaluated at its start and marked failed

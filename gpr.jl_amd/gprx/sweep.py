@@ -138,7 +138,7 @@ def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, c
 def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
               max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
               trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise", dataset=None,
-              loo: bool = False) -> dict:
+              loo: bool = False, objective: str = "mll") -> dict:
     """One (mechanism, N, variant) group for this rank's trials: device optimise of every GP,
     then the variant's evaluation.  Returns per-trial arrays (n_local, ...) and timings.
     trials: prebuilt local_trials-shaped inputs (the hyper-parameter search's), else noise.jl's.
@@ -151,7 +151,10 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     dataset: take the trials from simulated datasets (local_trials) and the truth from their sfuture.
     loo: also return loo_logp (n_local, G), logp_LOO of every GP at its minimiser (GPBatch.loo right
     after the optimiser's refit, in every device batch; NaN where the refit failed).  Recorded only:
-    nothing selects by it.  Off: the result is what it was, key for key."""
+    nothing selects by it.  Off: the result is what it was, key for key.
+    objective: what the optimiser minimises -- "mll" (the default: -mll on the device state machine, as
+    ever) or "loo" (-logp_LOO, optim.optimize_batch's host loop over GPBatch.loo_grad); the result's keys
+    are the same."""
     if md_rollout not in MD_ROLLOUTS:
         raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")
     if trials is None:
@@ -165,7 +168,8 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     parts = []
     for lo, hi, nd in plan:
         rb = shard.RankBatch(trials[lo:hi], ctx=ctx, dev_trials=nd)
-        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout, loo)
+        part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout, loo,
+                          objective)
         if keep:
             part.update(rb=rb, trials=trials)
         else:
@@ -180,14 +184,18 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     return out
 
 
-def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise", loo=False) -> dict:
+def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise", loo=False,
+               objective="mll") -> dict:
     """run_group's work for the trials of one device batch rb."""
     from .optim import LBFGS, Options
 
     n = len(trials)
     t0 = time.perf_counter()
     th0 = np.stack([t["theta"] for t in trials])
-    opt = rb.optimize(th0, LBFGS(), Options(max_evals=max_evals, time_limit=time_limit))
+    if objective == "mll":
+        opt = rb.optimize(th0, LBFGS(), Options(max_evals=max_evals, time_limit=time_limit))
+    else:
+        opt = rb.optimize(th0, LBFGS(), Options(max_evals=max_evals, time_limit=time_limit), objective=objective)
     t_opt = time.perf_counter() - t0
     G = rb.G
     # the batch is factorised at the minimisers (rb.optimize's closing evaluation)

@@ -11,6 +11,7 @@ experiment scripts (examples/noise.jl, examples/hyperparameter.jl) stay textuall
     predict_f(gp, x*; full_cov=true)      -> gprx_gp_predict_cov
     rand(gp, x*, n)                       -> gprx_gp_sample (randn on the Julia side)
     predict_LOO(gp), logp_LOO(gp)         -> gprx_gp_loo
+    dlogpdθ_LOO(gp)                       -> gprx_gp_loo_grad   [ext, recalled]
 
 plus `GPRx.optimize_all!(gps)`: the loop `for gp in gps; optimize!(gp, LBFGS(linesearch =
 BackTracking(order=2)), Optim.Options(time_limit=10.)); end` of CPnoise.jl:37-43 as ONE
@@ -188,6 +189,24 @@ function GaussianProcesses.logp_LOO(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd})
     check(ccall((:gprx_gp_loo, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
                 handle(gp).ptr, C_NULL, C_NULL, lp), gp)
     return lp[]
+end
+
+# dlogpdθ_LOO(gp) [ext, recalled: GaussianProcesses crossvalidation.jl pairs logp_LOO with a gradient of
+# this name; the package source was not available to confirm it]: the gradient of logp_LOO with respect
+# to the hyper-parameters in get_params' order [logNoise, kernel...] (the prior mean has no parameters
+# here), from the device factorisation of the last evaluation (gprx_gp_loo_grad: R&W 5.13 contracted
+# against dK/dθ).  The batch form is gprx_batch_loo_grad.
+function GaussianProcesses.dlogpdθ_LOO(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd})
+    g = zeros(size(gp.x, 1) + 2)
+    check(ccall((:gprx_gp_loo_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                handle(gp).ptr, C_NULL, g), gp)
+    return g
+end
+function loo_grad_batch(batch::Ptr{Cvoid}, B::Integer, d::Integer)
+    logp, grad, status = zeros(B), zeros(d + 2, B), zeros(Cint, B)
+    rc = ccall((:gprx_batch_loo_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+               batch, logp, grad, status)
+    return rc, logp, grad, status
 end
 
 # predictdynamicsmin (examples/utils/predictdynamics.jl:30-102) for all test observations of one

@@ -16,6 +16,7 @@
  *   gprx_gp_predict_cov, gprx_gp_sample   [ext] predict_f(gp, x; full_cov=true), rand(gp, x, n): on
  *                      every GPE (CPnoise.jl:40); the reference's scripts use the mean only
  *   gprx_gp_loo / gprx_batch_loo   [ext] predict_LOO(gp), logp_LOO(gp) (crossvalidation.jl), on every GPE
+ *   gprx_gp_loo_grad / gprx_batch_loo_grad   [ext, recalled] dlogpdtheta_LOO(gp) (crossvalidation.jl)
  *   gprx_rollout_min   predictdynamicsmin             examples/utils/predictdynamics.jl:30-102
  *   gprx_batch_*       the G per-output GPs of a trial (CPnoise.jl:37-43) and the trial loop
  *                      (examples/parallel/core.jl:28) evaluated as one device batch
@@ -217,6 +218,29 @@ int gprx_batch_cov_bytes(int B, int N, int M_max, uint64_t* bytes);
  * The launches go straight on the context stream (stats "loo_diag", "loo_final").                */
 int gprx_batch_loo(gprx_batch* batch, double* mu, double* var, double* logp_i, double* logp, int* status);
 
+/* ---- gradient of the leave-one-out log predictive probability ------------------------------- */
+/* [ext, recalled: the package source was not available] dlogpdtheta_LOO(gp) of GaussianProcesses'
+ * crossvalidation.jl: the gradient of gprx_batch_loo's logp with respect to the hyper-parameters,
+ * from the factorisation and theta of the last evaluation (no refit).  With K = Kf + (sn2 + eps) I,
+ * q_i = [K^-1]_ii, alpha = K^-1 y, c_i = (1/q_i + alpha_i^2/q_i^2)/2, r_i = alpha_i/q_i,
+ * beta = K^-1 r and C = diag(c), Rasmussen & Williams 5.13 in contracted form is
+ *   dlogp = sum_kl dK_kl W'_kl,   W' = (beta alpha^T + alpha beta^T)/2 - K^-1 C K^-1
+ * with dK/dlog sn = 2 sn2 I, dK/dlog ell_p = Kf o (x_p - x_p')^2 / ell_p^2, dK/dlog sf = 2 Kf: the
+ * marginal likelihood gradient's contraction with 2 W' in place of alpha alpha^T - K^-1.
+ * Host outputs, any may be NULL: logp[B] (bit for bit gprx_batch_loo's), grad[B*(d+2)] in the order
+ * of theta, [log sn, log ell_1..d, log sf] (a dimension that gprx_batch_set_train found constant
+ * gets exactly 0, as in the marginal likelihood's gradient), status[B] (that evaluation's per-slot
+ * status).  GPRX_NOT_READY before a successful factorisation; GPRX_INVALID_ARGUMENT for a NULL
+ * batch.  A slot whose status in that evaluation was not GPRX_OK gets NaN in logp and its gradient
+ * row; the other slots are unaffected.  Returns GPRX_OK or the first failing slot's status.  The
+ * results are bitwise reproducible and do not depend on B or on the slot's place in the batch.
+ * The call overwrites the factorisation workspace Lw (with K^-1 diag(sqrt c)), which nothing reads
+ * before the next evaluation rewrites it: predictions, alpha and gprx_batch_loo after it return what
+ * they return without it.  The small vectors come from the context's scratch buffer;
+ * gprx_batch_bytes is unchanged.  The launches go straight on the context stream (stats
+ * "loo_diag", "loo_final", "loo_kinv", "loo_beta", "loo_grad", "loo_grad_final").                 */
+int gprx_batch_loo_grad(gprx_batch* batch, double* logp, double* grad, int* status);
+
 /* ---- hyper-parameter optimisation on the device ------------------------------------------- */
 /* GaussianProcesses.optimize!(gp, LBFGS(linesearch=BackTracking(order=2)), Optim.Options(...))
  * (examples/maximal_coordinates/CPnoise.jl:41 and its 15 siblings) for every slot of a batch:
@@ -297,6 +321,9 @@ int gprx_gp_sample(gprx_gp* gp, const double* Xs, int M, const double* Z, int S,
 /* [ext] predict_LOO(gp): mu[N], var[N]; logp_LOO(gp): logp[1]; any may be NULL (gprx_batch_loo on
  * the batch of one, at the factorisation of the last lml call).                                  */
 int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp);
+/* [ext, recalled] dlogpdtheta_LOO(gp): logp[1], grad[d+2] in the order of theta; either may be NULL
+ * (gprx_batch_loo_grad on the batch of one, at the factorisation of the last lml call).         */
+int gprx_gp_loo_grad(gprx_gp* gp, double* logp, double* grad);
 
 /* the single GP's underlying batch of one (slot 0), e.g. for gprx_rollout_min              */
 gprx_batch* gprx_gp_batch(gprx_gp* gp);
