@@ -1098,9 +1098,24 @@ void gprx_opt_defaults(gprx_opt_options* o) {
   o->rho_lo = 0.1;
 }
 
-int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_options* opt, double* theta_out,
-                        double* minimum, int* iterations, int* f_calls, int* g_calls, int* stopped, int* rounds) {
-  if (!b || !theta0) return GPRX_INVALID_ARGUMENT;
+// The leave-one-out launches (defined with gprx_batch_loo_grad below), which the optimiser's rounds
+// share with it: the workspace's pieces in the context scratch and the six launches.
+static int ctx_scratch(gprx_ctx* c, size_t need, char** base);
+struct LooWs {
+  double *kinv, *mu, *var, *lp, *beta, *bp, *gp, *out, *logp;
+};
+static size_t loo_ws_bytes(const DevBatch& db);
+static LooWs loo_ws_at(char* base, const DevBatch& db);
+static void loo_grad_launches(gprx_ctx* c, const DevBatch& db, const LooWs& w);
+
+// gprx_batch_optimize and gprx_batch_optimize_obj.  objective GPRX_OBJ_LOO: a round is the evaluation
+// without the marginal-likelihood gradient (gram .. finalize) followed by the six leave-one-out
+// launches, all under the round's mask, and k_lbfgs reads the slot's answer from the leave-one-out
+// result rows ([logp, grad(d+2)], db.out's layout) through a DevBatch copy whose out points at them.
+static int batch_optimize(gprx_batch* b, int objective, const double* theta0, const gprx_opt_options* opt, double* theta_out,
+                          double* minimum, int* iterations, int* f_calls, int* g_calls, int* stopped, int* rounds) {
+  if (!b || !theta0 || (objective != GPRX_OBJ_MLL && objective != GPRX_OBJ_LOO)) return GPRX_INVALID_ARGUMENT;
+  const bool loo = objective == GPRX_OBJ_LOO;
   gprx_ctx* c = b->ctx;
   std::lock_guard<std::mutex> g(c->mu);
   if (!b->have_train) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_optimize before gprx_batch_set_train");
@@ -1169,9 +1184,19 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
   PinBlock trbuf = trr > 0 ? pin_block((size_t)trr * trs * sizeof(double)) : PinBlock();
   if (trr > 0 && !trbuf) return set_err(c, GPRX_OUT_OF_MEMORY, "gprx_batch_optimize: trace buffer");
   double* h_tr = (double*)trbuf.get();
+  // the leave-one-out workspace, sized once: ctx_scratch may free and reallocate, so no round calls it
+  LooWs lw{};
+  if (loo) {
+    char* base = nullptr;
+    int rc = ctx_scratch(c, loo_ws_bytes(db), &base);
+    if (rc) return rc;
+    lw = loo_ws_at(base, db);
+  }
   HIPCHK(c, hipMemcpyAsync(th0d, theta0, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   gprx::launch_lbfgs(a, db, 1, c->stream);
   db.active = a.active;
+  DevBatch dba = db;  // what k_lbfgs reads its answers from: the evaluation's rows, or the leave-one-out rows
+  if (loo) dba.out = lw.out;
   const auto t0 = std::chrono::steady_clock::now();
   int nr = 0;
   for (;;) {
@@ -1182,17 +1207,18 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
     if (!act) break;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     a.time_up = (o.time_limit >= 0.0 && el > o.time_limit) ? 1 : 0;  // false for NaN
-    int rc = run_eval(b, true, false, true);
+    int rc = run_eval(b, !loo, false, true);
     if (rc) return rc;
+    if (loo) loo_grad_launches(c, db, lw);
     collect(c);
     if (nr < trr) {
       double* h = h_tr + (size_t)nr * trs;
       memcpy(&tr_act[(size_t)nr * B], h_act, (size_t)B * sizeof(int));
       HIPCHK(c, hipMemcpyAsync(h, db.theta, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h + (size_t)B * n, db.out, (size_t)B * (n + 1) * sizeof(double), hipMemcpyDeviceToHost,
+      HIPCHK(c, hipMemcpyAsync(h + (size_t)B * n, dba.out, (size_t)B * (n + 1) * sizeof(double), hipMemcpyDeviceToHost,
                                c->stream));
     }
-    gprx::launch_lbfgs(a, db, 0, c->stream);
+    gprx::launch_lbfgs(a, dba, 0, c->stream);
     HIPCHK(c, hipGetLastError());
     ++nr;
   }
@@ -1208,7 +1234,7 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  if (trr > 0) {  // [active, theta(n), mll, dmll(n)] per slot and round; NaN beyond the last round
+  if (trr > 0) {  // [active, theta(n), mll, dmll(n)] per slot and round (logp, dlogp for GPRX_OBJ_LOO); NaN beyond the last round
     const size_t w = 2 * (size_t)n + 2;
     for (int r = 0; r < trr; ++r)
       for (int s = 0; s < B; ++s) {
@@ -1246,6 +1272,17 @@ int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_opti
                                  gprx_status_string(first));
   b->factored = true;
   return GPRX_OK;
+}
+
+int gprx_batch_optimize(gprx_batch* b, const double* theta0, const gprx_opt_options* opt, double* theta_out,
+                        double* minimum, int* iterations, int* f_calls, int* g_calls, int* stopped, int* rounds) {
+  return batch_optimize(b, GPRX_OBJ_MLL, theta0, opt, theta_out, minimum, iterations, f_calls, g_calls, stopped, rounds);
+}
+
+int gprx_batch_optimize_obj(gprx_batch* b, int objective, const double* theta0, const gprx_opt_options* opt,
+                            double* theta_out, double* minimum, int* iterations, int* f_calls, int* g_calls, int* stopped,
+                            int* rounds) {
+  return batch_optimize(b, objective, theta0, opt, theta_out, minimum, iterations, f_calls, g_calls, stopped, rounds);
 }
 
 int gprx_batch_set_opt_trace(gprx_batch* b, double* trace, int max_rounds, int64_t capacity) {
@@ -1381,6 +1418,36 @@ int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp) {
 // beta partials (B x nt x Npad), the unit partials (B x ngu x gps) and the result rows (B x (d + 3)).
 // P = K^-1 diag(sqrt c) goes to Lw, which only the factorisation reads and every evaluation rewrites.
 // Not part of the captured evaluation graphs: six launches straight on the context stream.
+static size_t loo_ws_bytes(const DevBatch& db) {
+  const size_t rows = (size_t)db.B * db.Npad;
+  return (5 * rows + db.B + rows * db.nt + (size_t)db.B * db.ngu * db.gps + (size_t)db.B * (db.d + 3)) * sizeof(double);
+}
+static LooWs loo_ws_at(char* base, const DevBatch& db) {
+  const size_t rows = (size_t)db.B * db.Npad;
+  const size_t n_bp = rows * db.nt, n_gp = (size_t)db.B * db.ngu * db.gps, n_out = (size_t)db.B * (db.d + 3);
+  LooWs w;
+  w.kinv = (double*)base;
+  w.mu = w.kinv + rows, w.var = w.mu + rows, w.lp = w.var + rows, w.beta = w.lp + rows;
+  w.bp = w.beta + rows, w.gp = w.bp + n_bp, w.out = w.gp + n_gp, w.logp = w.out + n_out;
+  return w;
+}
+// the six launches on the context stream, for the slots of db's evaluation mask (all of them without
+// one); the caller checks hipGetLastError
+static void loo_grad_launches(gprx_ctx* c, const DevBatch& db, const LooWs& w) {
+  const int d = db.d;
+  const double B = db.B, N = db.N, Np = db.Npad, tri = N * (N + 1.0) / 2.0;
+  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, w.kinv, c->stream); });
+  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
+        [&] { gprx::launch_loo_final(db, w.kinv, w.mu, w.var, w.lp, w.logp, c->stream); });
+  timed(c, c->stream, "loo_kinv", B * (Np * Np * Np / 3.0 + 4.0 * Np * Np), B * 8.0 * (1.5 * Np * Np + 2.0 * db.nt * Np),
+        [&] { gprx::launch_loo_kinv(db, w.kinv, w.bp, c->stream); });
+  timed(c, c->stream, "loo_beta", B * db.nt * Np, B * 8.0 * (db.nt + 1.0) * Np, [&] { gprx::launch_loo_beta(db, w.bp, w.beta, c->stream); });
+  timed(c, c->stream, "loo_grad", B * (Np * Np * Np + Np * Np * db.da + 6.0 * Np * Np),
+        B * 8.0 * (1.5 * Np * Np + Np * db.da), [&] { gprx::launch_loo_grad(db, w.beta, w.gp, c->stream); });
+  timed(c, c->stream, "loo_grad_final", B * (double)db.ngu * db.gps, B * 8.0 * ((double)db.ngu * db.gps + d + 3),
+        [&] { gprx::launch_loo_grad_final(db, w.gp, w.logp, w.out, c->stream); });
+}
+
 int gprx_batch_loo_grad(gprx_batch* b, double* logp, double* grad, int* status) {
   if (!b) return GPRX_INVALID_ARGUMENT;
   gprx_ctx* c = b->ctx;
@@ -1389,25 +1456,12 @@ int gprx_batch_loo_grad(gprx_batch* b, double* logp, double* grad, int* status) 
   if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
   const DevBatch& db = b->db;
   const int d = db.d;
-  const size_t rows = (size_t)db.B * db.Npad;
-  const size_t n_bp = rows * db.nt, n_gp = (size_t)db.B * db.ngu * db.gps, n_out = (size_t)db.B * (d + 3);
   char* base = nullptr;
-  int rc = ctx_scratch(c, (5 * rows + db.B + n_bp + n_gp + n_out) * sizeof(double), &base);
+  int rc = ctx_scratch(c, loo_ws_bytes(db), &base);
   if (rc) return rc;
-  double* kinv = (double*)base;
-  double *d_mu = kinv + rows, *d_var = d_mu + rows, *d_lp = d_var + rows, *d_beta = d_lp + rows;
-  double *d_bp = d_beta + rows, *d_gp = d_bp + n_bp, *d_out = d_gp + n_gp, *d_logp = d_out + n_out;
-  const double B = db.B, N = db.N, Np = db.Npad, tri = N * (N + 1.0) / 2.0;
-  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, kinv, c->stream); });
-  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
-        [&] { gprx::launch_loo_final(db, kinv, d_mu, d_var, d_lp, d_logp, c->stream); });
-  timed(c, c->stream, "loo_kinv", B * (Np * Np * Np / 3.0 + 4.0 * Np * Np), B * 8.0 * (1.5 * Np * Np + 2.0 * db.nt * Np),
-        [&] { gprx::launch_loo_kinv(db, kinv, d_bp, c->stream); });
-  timed(c, c->stream, "loo_beta", B * db.nt * Np, B * 8.0 * (db.nt + 1.0) * Np, [&] { gprx::launch_loo_beta(db, d_bp, d_beta, c->stream); });
-  timed(c, c->stream, "loo_grad", B * (Np * Np * Np + Np * Np * db.da + 6.0 * Np * Np),
-        B * 8.0 * (1.5 * Np * Np + Np * db.da), [&] { gprx::launch_loo_grad(db, d_beta, d_gp, c->stream); });
-  timed(c, c->stream, "loo_grad_final", B * (double)db.ngu * db.gps, B * 8.0 * ((double)db.ngu * db.gps + d + 3),
-        [&] { gprx::launch_loo_grad_final(db, d_gp, d_logp, d_out, c->stream); });
+  const LooWs lw = loo_ws_at(base, db);
+  double* d_out = lw.out;
+  loo_grad_launches(c, db, lw);
   HIPCHK(c, hipGetLastError());
   const size_t ro = (size_t)(d + 3) * sizeof(double);
   if (logp) HIPCHK(c, hipMemcpy2DAsync(logp, sizeof(double), d_out, ro, sizeof(double), db.B, hipMemcpyDeviceToHost, c->stream));

@@ -37,7 +37,7 @@ namespace gprx {
 __host__ __device__ inline int loo_units(int nt) { return (nt + 1) / 2; }
 __global__ __launch_bounds__(NTHR) void k_loo_diag(DevBatch db, double* kinv) {
   int slot, p;
-  if (!map_block(blockIdx.x, db.B, loo_units(db.nt), slot, p)) return;
+  if (!map_slot(db, loo_units(db.nt), slot, p)) return;  // a masked slot: before the first load
   typedef double d2 __attribute__((ext_vector_type(2)));
   const int l = threadIdx.x & 63, rp = l & 31, cp = l >> 5;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -118,6 +118,7 @@ __global__ __launch_bounds__(NTHR) void k_loo_final(DevBatch db, const double* k
                                                     double* logp) {
   __shared__ double ps[NTHR], pe[NTHR];
   const int slot = blockIdx.x, tid = threadIdx.x, N = db.N;
+  if (!slot_active(db, slot)) return;  // block-uniform, before the first barrier: the slot's rows stay as they are
   const size_t ro = (size_t)slot * db.Npad;
   if (db.status[slot] != 0) {  // block-uniform
     const double nan = __builtin_nan("");

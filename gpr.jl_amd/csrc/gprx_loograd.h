@@ -186,7 +186,7 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
                                                                                               double* bpart) {
   __shared__ __attribute__((aligned(16))) double lw[4 * LKW];
   int slot, job;
-  if (!map_block(blockIdx.x, db.B, db.nlj, slot, job)) return;
+  if (!map_slot(db, db.nlj, slot, job)) return;
   const int* jb = db.lauum_order + (size_t)job * 2 * LU;
   double* wl = lw + (threadIdx.x >> 6) * LKW;
   loo_kinv_unit(db, slot, jb, kinv, bpart, wl);
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 // ============================================================================================
 __global__ __launch_bounds__(TS) void k_loo_beta(DevBatch db, const double* bpart, double* beta) {
   int slot, x;
-  if (!map_block(blockIdx.x, db.B, db.nt, slot, x)) return;
+  if (!map_slot(db, db.nt, slot, x)) return;
   const int nt = db.nt, l = threadIdx.x;
   const double* bp = bpart + ((size_t)slot * nt + x) * nt * TS;
   double s = 0.0;
@@ -386,7 +386,7 @@ __device__ __forceinline__ void loo_grad_unit(const DevBatch& db, int slot, cons
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_loo_grad(DevBatch db, const double* beta,
                                                                                               double* gpart) {
   int slot, job;
-  if (!map_block(blockIdx.x, db.B, db.nlj, slot, job)) return;
+  if (!map_slot(db, db.nlj, slot, job)) return;
   const int* jb = db.lauum_order + (size_t)job * 2 * LU;
   const int nu = jb[LU] >= 0 ? 2 : 1;  // block-uniform: the folded short unit
   loo_grad_unit(db, slot, jb, beta, gpart);
@@ -406,6 +406,7 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 __global__ __launch_bounds__(NTHR) void k_loo_grad_final(DevBatch db, const double* gpart, const double* logp, double* out_all) {
   __shared__ double pr[4];
   const int slot = blockIdx.x, tid = threadIdx.x, d = db.d;
+  if (!slot_active(db, slot)) return;  // block-uniform, before the first barrier: the slot's row stays as it is
   double* out = out_all + (size_t)slot * (d + 3);
   if (db.status[slot] != 0) {  // block-uniform
     for (int e = tid; e < d + 3; e += NTHR) out[e] = __builtin_nan("");

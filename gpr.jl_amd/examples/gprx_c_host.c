@@ -10,6 +10,8 @@
  *   the G outputs of the trial as one batch (one gprx_batch_run):        batch_mll
  *   optimize! of every output on the device, f_calls_limit 15:             opt_min, opt_evals,
  *                                                                        opt_theta0 (slot 0)
+ *   the same with the leave-one-out objective (gprx_batch_optimize_obj,
+ *   GPRX_OBJ_LOO: minimises -logp_LOO), from the same start:             loo_min, loo_evals
  * Exit status 0 on success; on failure the gprx status string goes to stderr.
  */
 #include <stdint.h>
@@ -124,6 +126,12 @@ int main(int argc, char** argv) {
   print_row("opt_min", fmin, G);
   print_row("opt_evals", ev, G);
   print_row("opt_theta0", thx, d + 2);
+  /* ... and minimising -logp_LOO (leave-one-out log predictive probability) instead of -mll */
+  rc = gprx_batch_optimize_obj(b, GPRX_OBJ_LOO, th, &opt, thx, fmin, NULL, fc, gc, NULL, &rounds);
+  if (rc) return fail("gprx_batch_optimize_obj", rc, ctx);
+  for (int g = 0; g < G; ++g) ev[g] = fc[g];
+  print_row("loo_min", fmin, G);
+  print_row("loo_evals", ev, G);
   free(thx);
   free(fmin);
   free(fc);

@@ -40,6 +40,9 @@ OPT_ACTIVE_DIMS = 5  # id 4 is retired and not reused
 STOP_NAMES = {0: "iterations", 1: "g_tol", 2: "x_tol", 3: "f_tol", 4: "linesearch", 5: "max_evals", 6: "time_limit",
               7: "nan_gradient"}
 STOP_CONVERGED = 0x100
+# gprx_batch_optimize_obj: GPRX_OBJ_MLL, GPRX_OBJ_LOO
+OBJ_MLL = 0
+OBJ_LOO = 1
 
 
 class OptOptions(C.Structure):
@@ -86,6 +89,7 @@ SIGNATURES = {
     "gprx_batch_loo_grad": (C.c_int, [_vp, _dp, _dp, _ip]),
     "gprx_opt_defaults": (None, [C.POINTER(OptOptions)]),
     "gprx_batch_optimize": (C.c_int, [_vp, _dp, C.POINTER(OptOptions), _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
+    "gprx_batch_optimize_obj": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(OptOptions), _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "gprx_batch_set_opt_trace": (C.c_int, [_vp, _dp, C.c_int, C.c_int64]),
     "gprx_gp_create": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, C.POINTER(_vp)]),
     "gprx_gp_destroy": (None, [_vp]),

@@ -218,7 +218,8 @@ class GPBatch:
             L.check(rc, self.ctx.h)
         return dict(mll=mll, grad=g, mu=mu, var=var, status=st, info=info)
 
-    def optimize(self, theta0, method=None, options=None, refit: bool = True, trace_rounds: int = 0):
+    def optimize(self, theta0, method=None, options=None, refit: bool = True, trace_rounds: int = 0,
+                 objective: str = "mll"):
         """GaussianProcesses.optimize!(gp, LBFGS(linesearch=BackTracking(order=2)), options) for
         every slot (CPnoise.jl:41), on the device (k_lbfgs: gprx/optim.py's algorithm as a per-slot
         state machine, lock-step over the batch).  method / options: gprx.optim.LBFGS / Options.
@@ -227,9 +228,17 @@ class GPBatch:
         minimiser whose refit fails raises (update_target!'s PosDefException / ArgumentError) with
         the results attached as `err.results`; the batch is then left unfactorised.
         trace_rounds > 0 records the first rounds' evaluations (gprx_batch_set_opt_trace) in
-        `self.last_opt_trace`: (rounds, B, 2n+2) rows [active, theta(n), mll, dmll(n)], n = d+2."""
+        `self.last_opt_trace`: (rounds, B, 2n+2) rows [active, theta(n), mll, dmll(n)], n = d+2.
+        objective: "mll" (the default: minimise -mll, gprx_batch_optimize) or "loo": minimise -logp_LOO
+        on the same state machine (gprx_batch_optimize_obj with GPRX_OBJ_LOO: every round evaluates the
+        running slots without the marginal-likelihood gradient and then runs loo_grad()'s launches for
+        them); minima are then -logp_LOO and the trace rows hold logp and its gradient, as
+        optim.optimize_batch(objective="loo"), the host restatement, records them.  The refit is the
+        same either way.  Anything else raises ValueError before any device call."""
         from .optim import Result
 
+        if objective not in ("mll", "loo"):
+            raise ValueError(f"objective must be 'mll' or 'loo', not {objective!r}")
         o = opt_options(method, options, refit)
         theta0 = _f64(theta0)
         if theta0.ndim == 1:
@@ -246,8 +255,11 @@ class GPBatch:
             tr = np.full((int(trace_rounds), B, 2 * n + 2), np.nan)
             L.check(L.lib.gprx_batch_set_opt_trace(self.h, L.dptr(tr), int(trace_rounds), tr.size), self.ctx.h)
         try:
-            rc = L.lib.gprx_batch_optimize(self.h, L.dptr(theta0), C.byref(o), L.dptr(th), L.dptr(fmin), L.iptr(its),
-                                           L.iptr(fc), L.iptr(gc), L.iptr(stp), C.byref(rounds))
+            outs = (L.dptr(th), L.dptr(fmin), L.iptr(its), L.iptr(fc), L.iptr(gc), L.iptr(stp), C.byref(rounds))
+            if objective == "loo":
+                rc = L.lib.gprx_batch_optimize_obj(self.h, L.OBJ_LOO, L.dptr(theta0), C.byref(o), *outs)
+            else:
+                rc = L.lib.gprx_batch_optimize(self.h, L.dptr(theta0), C.byref(o), *outs)
         finally:
             if tr is not None:
                 L.lib.gprx_batch_set_opt_trace(self.h, None, 0, 0)

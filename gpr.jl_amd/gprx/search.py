@@ -106,8 +106,8 @@ def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, s
     """One (experiment, N) of parallelsearch for this rank's trials (sweep.run_group on the
     search's inputs).  Adds the per-trial raw start params (n_local, d+1).  loo: also loo_logp
     (n_local, G), logp_LOO of every GP at its minimiser (sweep.run_group); recorded, not used.
-    objective: "mll" (the default, unchanged) or "loo": the GPs minimise -logp_LOO on the host loop
-    (optim.optimize_batch over GPBatch.loo_grad); the result's keys are the same."""
+    objective: "mll" (the default, unchanged) or "loo": the GPs minimise -logp_LOO on the device
+    optimiser (GPBatch.optimize(objective="loo")); the result's keys are the same."""
     from .sweep import run_group
 
     mech, coords = split(exp)
@@ -216,7 +216,7 @@ def main(argv=None):
     ap.add_argument("--time-limit", type=float, default=float("nan"), help="seconds per group call (NaN: none)")
     ap.add_argument("--loo", action="store_true", help="record logp_LOO of every GP at its minimiser (loo_logp)")
     ap.add_argument("--objective", choices=("mll", "loo"), default="mll",
-                    help="what every GP's optimiser minimises: -mll (device LBFGS) or -logp_LOO (host loop)")
+                    help="what every GP's optimiser minimises on the device LBFGS: -mll or -logp_LOO")
     ap.add_argument("--out", default="gpurun_out/params_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,

@@ -272,17 +272,13 @@ class RankBatch:
         then one evaluation at the minimisers (update_target!, with prediction when the trials
         have test points).  A slot whose refit fails is reported in `status` (the reference's
         experiment throws and the trial is dropped, core.jl:41-46), the others stay valid.
-        objective="loo": minimise -logp_LOO instead, on the host loop (optim.optimize_batch: the device
-        state machine k_lbfgs knows the marginal likelihood only)."""
+        objective="loo": minimise -logp_LOO instead, in the same device call (k_lbfgs fed by the
+        leave-one-out launches, finished slots masked out of every round); optim.optimize_batch is the
+        host restatement it is held to."""
         if self.batch is None:
             return {}
         th0 = self._rows(theta0)
-        if objective == "mll":
-            res, rounds = self.batch.optimize(th0, method, options, refit=False)
-        else:
-            from .optim import optimize_batch
-
-            res, rounds = optimize_batch(self.batch, th0, method, options, objective=objective)
+        res, rounds = self.batch.optimize(th0, method, options, refit=False, objective=objective)
         thmin = np.stack([r.minimizer for r in res])
         ok = np.all(np.isfinite(thmin), axis=1)
         # a non-finite minimiser (NaN-gradient stop) is evaluated at its start and marked failed

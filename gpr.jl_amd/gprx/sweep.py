@@ -153,7 +153,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     after the optimiser's refit, in every device batch; NaN where the refit failed).  Recorded only:
     nothing selects by it.  Off: the result is what it was, key for key.
     objective: what the optimiser minimises -- "mll" (the default: -mll on the device state machine, as
-    ever) or "loo" (-logp_LOO, optim.optimize_batch's host loop over GPBatch.loo_grad); the result's keys
+    ever) or "loo" (-logp_LOO on the same state machine, GPBatch.optimize(objective="loo")); the result's keys
     are the same."""
     if md_rollout not in MD_ROLLOUTS:
         raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")

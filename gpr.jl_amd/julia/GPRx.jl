@@ -386,14 +386,20 @@ struct OptOptions
     rho_hi::Cdouble
     rho_lo::Cdouble
 end
+const OBJ_MLL, OBJ_LOO = Cint(0), Cint(1)  # include/gprx.h GPRX_OBJ_MLL, GPRX_OBJ_LOO
 const STOP = ("iterations", "g_tol", "x_tol", "f_tol", "linesearch", "max_evals", "time_limit", "nan_gradient")
 
 # optimize! for every GP of a trial (CPnoise.jl:37-43) in one device call: Optim LBFGS +
 # BackTracking(order=2) as k_lbfgs, one lock-step evaluation of all GPs per round.  `time_limit`
 # is per call (the reference's 10 s applies to each GP in turn).  Afterwards every GP holds its
 # minimiser (set_params! + update_mll!, as optimize! leaves it).  Returns one NamedTuple per GP.
+# objective = :mll minimises -mll (gprx_batch_optimize); :loo minimises -logp_LOO with dlogpdθ_LOO's
+# gradient on the same device state machine (gprx_batch_optimize_obj with GPRX_OBJ_LOO), and
+# `minimum` is then -logp_LOO at the minimiser.
 function optimize_all!(gps::Vector{<:GPE}; time_limit::Real=NaN, iterations::Integer=1000,
-                       max_evals::Integer=-1, g_abstol::Real=1e-8)
+                       max_evals::Integer=-1, g_abstol::Real=1e-8, objective::Symbol=:mll)
+    objective in (:mll, :loo) || throw(ArgumentError("objective must be :mll or :loo, not $(repr(objective))"))
+    obj = objective == :loo ? OBJ_LOO : OBJ_MLL
     B = length(gps)
     X1 = Matrix{Float64}(gps[1].x)
     d, N = size(X1)
@@ -418,10 +424,17 @@ function optimize_all!(gps::Vector{<:GPE}; time_limit::Real=NaN, iterations::Int
         fmin = zeros(B)
         its, fc, gc, stp = (zeros(Cint, B) for _ in 1:4)
         rounds = Ref{Cint}(0)
-        rc = ccall((:gprx_batch_optimize, LIB), Cint,
-                   (Ptr{Cvoid}, Ptr{Float64}, Ref{OptOptions}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint},
-                    Ptr{Cint}, Ptr{Cint}, Ref{Cint}),
-                   b[], th0, o, thx, fmin, its, fc, gc, stp, rounds)
+        if obj == OBJ_MLL
+            rc = ccall((:gprx_batch_optimize, LIB), Cint,
+                       (Ptr{Cvoid}, Ptr{Float64}, Ref{OptOptions}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint},
+                        Ptr{Cint}, Ptr{Cint}, Ref{Cint}),
+                       b[], th0, o, thx, fmin, its, fc, gc, stp, rounds)
+        else
+            rc = ccall((:gprx_batch_optimize_obj, LIB), Cint,
+                       (Ptr{Cvoid}, Cint, Ptr{Float64}, Ref{OptOptions}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint},
+                        Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ref{Cint}),
+                       b[], obj, th0, o, thx, fmin, its, fc, gc, stp, rounds)
+        end
         rc == OK || error("gprx_batch_optimize failed ($rc)")
         for (k, gp) in enumerate(gps)   # optimize!: set_params!(gp, minimizer); update_target!(gp)
             GaussianProcesses.set_params!(gp, thx[:, k])

@@ -294,6 +294,24 @@ void gprx_opt_defaults(gprx_opt_options* opt);
  * and a device / memory error write none of them.                                               */
 int gprx_batch_optimize(gprx_batch* batch, const double* theta0, const gprx_opt_options* opt, double* theta_out,
                         double* minimum, int* iterations, int* f_calls, int* g_calls, int* stopped, int* rounds);
+/* The same optimiser with the objective named.  GPRX_OBJ_MLL is gprx_batch_optimize itself (one body:
+ * the same results bit for bit).  GPRX_OBJ_LOO minimises -logp_LOO, the leave-one-out log predictive
+ * probability with gprx_batch_loo_grad's gradient: a round evaluates the running slots without the
+ * marginal-likelihood gradient (Gram, factorisation, alpha, finalize), runs the six leave-one-out
+ * launches for the same slots (stats "loo_diag" .. "loo_grad_final"; the workspace comes from the
+ * context's scratch buffer, sized once before the first round) and the state machines take
+ * f = -logp, g = -dlogp from those result rows; a failed slot or a non-finite point answers +Inf with a
+ * NaN gradient as ever.  minimum[B] is then -logp_LOO at the minimiser.  Arguments, outputs, stop
+ * codes, budget, time limit and the refit are gprx_batch_optimize's: with refit the call ends with one
+ * evaluation of every slot at its minimiser, marginal-likelihood gradient included, so predict, alpha,
+ * gprx_batch_loo and gprx_batch_loo_grad answer for the minimisers.  Any other objective value is
+ * GPRX_INVALID_ARGUMENT and writes no output.  A registered trace's rows hold [active, theta, logp,
+ * dlogp] in GPRX_OBJ_LOO rounds.                                                                 */
+#define GPRX_OBJ_MLL 0 /* -mll: what gprx_batch_optimize minimises */
+#define GPRX_OBJ_LOO 1 /* -logp_LOO (gprx_batch_loo_grad's logp and gradient) */
+int gprx_batch_optimize_obj(gprx_batch* batch, int objective, const double* theta0, const gprx_opt_options* opt,
+                            double* theta_out, double* minimum, int* iterations, int* f_calls, int* g_calls,
+                            int* stopped, int* rounds);
 /* Diagnostics: record the optimiser's evaluations.  With a host buffer of max_rounds * B * (2(d+2)+2)
  * doubles registered, every later gprx_batch_optimize on this batch writes, for round r < max_rounds
  * and slot b, at trace[(r*B + b) * (2(d+2)+2)]: [active (1/0: evaluated in this round), theta(d+2)
