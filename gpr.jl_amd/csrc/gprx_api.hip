@@ -85,6 +85,12 @@ struct gprx_batch {
   int* cov_st = nullptr;      // B
   double* h_cov = nullptr;    // pinned, B doubles + B ints: jitter and status
   int cov_mpad = 0;           // the Mpad the workspace was sized for (0: none)
+  // fold layout of gprx_batch_set_folds (CvArgs in gprx_internal.h): the device table, the ints between
+  // two slots' layouts (0: shared), the folds, the largest tile count of a slot; cv_folds = 0: none set
+  int* cv_tab = nullptr;
+  size_t cv_lstride = 0;
+  int cv_folds = 0;
+  int cv_njmax = 0;
   bool factored = false;
   bool have_train = false;
   bool have_test = false;
@@ -710,6 +716,7 @@ static void batch_free(gprx_batch* b) {
     if (b->gvalid[i]) (void)hipGraphExecDestroy(b->gexec[i]);
   bufs_free(train_bufs(*b));
   drop_test(b);
+  if (b->cv_tab) (void)hipFree(b->cv_tab);
   delete b;
 }
 
@@ -1485,6 +1492,159 @@ int gprx_batch_loo_grad(gprx_batch* b, double* logp, double* grad, int* status) 
 int gprx_gp_loo_grad(gprx_gp* gp, double* logp, double* grad) {
   if (!gp) return GPRX_INVALID_ARGUMENT;
   return gprx_batch_loo_grad(gp->batch, logp, grad, nullptr);
+}
+
+// ---- k-fold cross-validation (gprx_cvfold.h) ------------------------------------------------------
+// The layout table of CvArgs, built on the host for every layout (one, or one per slot) and uploaded
+// once.  It belongs to the batch and is not part of gprx_batch_bytes.
+int gprx_batch_set_folds(gprx_batch* b, const int* fold_of, size_t slot_stride, int nfolds) {
+  if (!b || !fold_of) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  const DevBatch& db = b->db;
+  const int N = db.N, Npad = db.Npad, nt = db.nt, F = nfolds;
+  if (F < 1) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_set_folds: nfolds < 1");
+  if (slot_stride != 0 && slot_stride != (size_t)N)
+    return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_set_folds: slot_stride must be 0 (shared) or N");
+  const int S = slot_stride ? db.B : 1;
+  // pass 1: fold sizes and starts, the packed order, the tile rows' first columns
+  std::vector<std::vector<int>> perm(S), fstart(S), rowlo(S);
+  int njmax = 0;
+  for (int s = 0; s < S; ++s) {
+    const int* fo = fold_of + (size_t)s * slot_stride;
+    std::vector<int> cnt(F, 0);
+    for (int i = 0; i < N; ++i) {
+      if (fo[i] < 0 || fo[i] >= F) return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_set_folds: fold id out of range");
+      ++cnt[fo[i]];
+    }
+    fstart[s].assign(F + 1, 0);
+    for (int f = 0; f < F; ++f) {
+      if (cnt[f] > GPRX_CVFOLD_MAX)
+        return set_err(c, GPRX_INVALID_ARGUMENT, "gprx_batch_set_folds: a fold of more than GPRX_CVFOLD_MAX points");
+      fstart[s][f + 1] = fstart[s][f] + cnt[f];
+    }
+    perm[s].assign(Npad, -1);
+    std::vector<int> at(fstart[s].begin(), fstart[s].end() - 1);
+    for (int i = 0; i < N; ++i) perm[s][at[fo[i]]++] = i;  // ascending i within a fold: a stable sort
+    rowlo[s].assign(nt, nt);
+    for (int f = 0; f < F; ++f) {
+      if (!cnt[f]) continue;
+      const int t0 = fstart[s][f] / gprx::TS, t1 = (fstart[s][f + 1] - 1) / gprx::TS;
+      for (int t = t0; t <= t1; ++t) rowlo[s][t] = std::min(rowlo[s][t], t0);
+    }
+    int nj = 0;
+    for (int t = 0; t < nt; ++t) nj += t - rowlo[s][t] + 1;  // every tile row holds a point: rowlo <= t
+    njmax = std::max(njmax, nj);
+  }
+  // pass 2: the tables, one after the other
+  const size_t ls = gprx::cv_tab_ints(Npad, nt, F, njmax);
+  std::vector<int> tab(ls * S);
+  for (int s = 0; s < S; ++s) {
+    int* p = tab.data() + ls * s;
+    std::copy(perm[s].begin(), perm[s].end(), p);
+    p += Npad;
+    std::copy(fstart[s].begin(), fstart[s].end(), p);
+    p += F + 1;
+    p[0] = 0;
+    for (int f = 0; f < F; ++f) {
+      const int m = fstart[s][f + 1] - fstart[s][f];
+      p[f + 1] = p[f] + m * m;  // <= N^2 < 2^31 (sizes_addressable)
+    }
+    p += F + 1;
+    std::copy(rowlo[s].begin(), rowlo[s].end(), p);
+    p += nt;
+    int* jobs = p + (nt + 1) + nt;
+    std::fill(jobs, jobs + 2 * (size_t)njmax, -1);
+    int nj = 0;
+    for (int t = 0; t < nt; ++t) {
+      p[t] = nj;
+      for (int u = rowlo[s][t]; u <= t; ++u, ++nj) jobs[2 * nj] = t, jobs[2 * nj + 1] = u;
+    }
+    p[nt] = nj;
+    p += nt + 1;
+    for (int t = 0; t < nt; ++t) {
+      int lo = N - 1;
+      for (int r = t * gprx::TS; r < (t + 1) * gprx::TS && r < N; ++r) lo = std::min(lo, perm[s][r]);
+      p[t] = lo / gprx::TS * gprx::TS;
+    }
+  }
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  // the new table first: a failed allocation (GPRX_OUT_OF_MEMORY) or upload leaves the batch's folds as they were
+  int* nt_tab = nullptr;
+  HIPCHK(c, hipMalloc(&nt_tab, tab.size() * sizeof(int)));
+  if (hipMemcpy(nt_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(nt_tab);
+    return set_err(c, GPRX_DEVICE_ERROR, "gprx_batch_set_folds: upload failed");
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch still reads the old table
+  if (b->cv_tab) (void)hipFree(b->cv_tab);
+  b->cv_tab = nt_tab;
+  b->cv_lstride = S > 1 ? ls : 0;
+  b->cv_folds = F;
+  b->cv_njmax = njmax;
+  return GPRX_OK;
+}
+
+// Workspace in the context scratch: the tiles (B x njmax x 4096), r, pvar, mu, var (B x Npad each),
+// logp_fold (B x F), logp (B), then the ints: the folds' statuses (B x F) and the slots' (B).  Not part
+// of the captured evaluation graphs: four launches straight on the context stream.
+int gprx_batch_cvfold(gprx_batch* b, double* mu, double* var, double* logp_fold, double* logp, int* status) {
+  if (!b) return GPRX_INVALID_ARGUMENT;
+  gprx_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!b->factored) return set_err(c, GPRX_NOT_READY, "cross-validation before a successful factorisation");
+  if (!b->cv_folds) return set_err(c, GPRX_NOT_READY, "cross-validation before gprx_batch_set_folds");
+  if (hipSetDevice(c->device) != hipSuccess) return GPRX_DEVICE_ERROR;
+  const DevBatch& db = b->db;
+  const int F = b->cv_folds, nB = db.B;
+  const size_t rows = (size_t)nB * db.Npad, nfl = (size_t)nB * F, ntl = (size_t)nB * b->cv_njmax * gprx::TS * gprx::TS;
+  char* base = nullptr;
+  int rc = ctx_scratch(c, (ntl + 4 * rows + nfl + nB) * sizeof(double) + (nfl + nB) * sizeof(int), &base);
+  if (rc) return rc;
+  gprx::CvArgs a;
+  a.tab = b->cv_tab, a.lstride = b->cv_lstride, a.F = F, a.njmax = b->cv_njmax;
+  a.tiles = (double*)base;
+  a.r = a.tiles + ntl, a.pvar = a.r + rows, a.mu = a.pvar + rows, a.var = a.mu + rows;
+  a.lpf = a.var + rows, a.logp = a.lpf + nfl;
+  a.fst = (int*)(a.logp + nB), a.st = a.fst + nfl;
+  const double B = nB, N = db.N, Np = db.Npad;
+  double tiles = 0.0, m2 = 0.0, m3 = 0.0;  // of the layout the statistics are estimated for: an even split
+  {
+    const double m = N / F;
+    tiles = b->cv_njmax, m2 = F * m * m, m3 = F * m * m * m;
+  }
+  timed(c, c->stream, "cv_pack", 0.0, B * 8.0 * 1.5 * Np * Np, [&] { gprx::launch_cv_pack(db, a, c->stream); });
+  timed(c, c->stream, "cv_kinv", B * tiles * 2.0 * 64.0 * 64.0 * Np / 2.0, B * 8.0 * tiles * (64.0 * Np + 4096.0),
+        [&] { gprx::launch_cv_kinv(db, a, c->stream); });
+  timed(c, c->stream, "cv_fold", B * m3, B * 8.0 * 3.0 * m2, [&] { gprx::launch_cv_fold(db, a, c->stream); });
+  timed(c, c->stream, "cv_final", B * (2.0 * N + F), B * 8.0 * (5.0 * N + F), [&] { gprx::launch_cv_final(db, a, c->stream); });
+  HIPCHK(c, hipGetLastError());
+  const size_t w = (size_t)db.N * sizeof(double), p = (size_t)db.Npad * sizeof(double);
+  std::vector<int> hst(nB);
+  if (mu) HIPCHK(c, hipMemcpy2DAsync(mu, w, a.mu, p, w, nB, hipMemcpyDeviceToHost, c->stream));
+  if (var) HIPCHK(c, hipMemcpy2DAsync(var, w, a.var, p, w, nB, hipMemcpyDeviceToHost, c->stream));
+  if (logp_fold) HIPCHK(c, hipMemcpyAsync(logp_fold, a.lpf, nfl * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (logp) HIPCHK(c, hipMemcpyAsync(logp, a.logp, (size_t)nB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hst.data(), a.st, (size_t)nB * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  collect(c);
+  int first = GPRX_OK;
+  for (int s = 0; s < nB; ++s) {
+    if (status) status[s] = hst[s];
+    if (hst[s] != GPRX_OK && first == GPRX_OK) first = hst[s];
+  }
+  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_cvfold: ") + gprx_status_string(first));
+  return first;
+}
+
+int gprx_gp_set_folds(gprx_gp* gp, const int* fold_of, int nfolds) {
+  if (!gp) return GPRX_INVALID_ARGUMENT;
+  return gprx_batch_set_folds(gp->batch, fold_of, 0, nfolds);
+}
+
+int gprx_gp_cvfold(gprx_gp* gp, double* mu, double* var, double* logp_fold, double* logp) {
+  if (!gp) return GPRX_INVALID_ARGUMENT;
+  return gprx_batch_cvfold(gp->batch, mu, var, logp_fold, logp, nullptr);
 }
 
 // The ngroups x G GPs of a rollout (entry point fn), gathered from batch slots of this context that

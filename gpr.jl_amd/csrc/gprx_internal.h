@@ -420,6 +420,39 @@ void launch_loo_kinv(const DevBatch& b, const double* kinv, double* bpart, hipSt
 void launch_loo_beta(const DevBatch& b, const double* bpart, double* beta, hipStream_t s);
 void launch_loo_grad(const DevBatch& b, const double* beta, double* gpart, hipStream_t s);
 void launch_loo_grad_final(const DevBatch& b, const double* gpart, const double* logp, double* out, hipStream_t s);
+// k-fold cross-validation (gprx_cvfold.h).  The fold layout of a batch as gprx_batch_set_folds builds
+// it on the host: one table of ints per layout (lstride = 0: one layout shared by all slots), the
+// parts in this order.  "Packed order" lists the points fold after fold, each fold's points in
+// ascending index (a stable sort by fold id), so a fold is a contiguous range of packed positions.
+//   perm   [Npad]      the point at a packed position (-1 for the positions >= N)
+//   fstart [F + 1]     packed position of a fold's first point
+//   foff   [F + 1]     sum of m_g^2 over the folds g before f: the fold's m x m square in Lw
+//   rowlo  [nt]        the first tile column a fold reaches from tile row ti of the packed K^-1
+//   rowoff [nt + 1]    index of tile (ti, rowlo[ti]) among the slot's tiles; rowoff[nt] = their number
+//   kmin   [nt]        64 floor(min perm / 64) over the tile row's points: the packed rows are 0 before it
+//   jobs   [2 njmax]   (ti, tj) of tile j, rows ascending and columns ascending within a row; -1 beyond
+struct CvArgs {
+  const int* tab;
+  size_t lstride;  // ints between the layouts of two slots, or 0
+  int F, njmax;
+  double* tiles;   // B x njmax x [64][64] column-major tiles of the packed K^-1 (the folds' Q blocks)
+  double* r;       // B x Npad  r = Q^-1 a per fold, packed order
+  double* pvar;    // B x Npad  diag(Q^-1), packed order
+  double* lpf;     // B x F     log p(y_V | y_-V)
+  int* fst;        // B x F     0, or 1: the fold's block is not positive definite
+  double* mu;      // B x Npad  the outputs in point order
+  double* var;     // B x Npad
+  double* logp;    // B
+  int* st;         // B         0, 1 (a fold failed), or the status of the slot's failed evaluation
+};
+__host__ __device__ inline size_t cv_tab_ints(int Npad, int nt, int F, int njmax) {
+  return (size_t)Npad + 2 * (size_t)(F + 1) + 3 * (size_t)nt + 1 + 2 * (size_t)njmax;
+}
+constexpr int CVFOLD_MAX = 1024;  // GPRX_CVFOLD_MAX: one workgroup factors one fold's block
+void launch_cv_pack(const DevBatch& b, const CvArgs& a, hipStream_t s);
+void launch_cv_kinv(const DevBatch& b, const CvArgs& a, hipStream_t s);
+void launch_cv_fold(const DevBatch& b, const CvArgs& a, hipStream_t s);
+void launch_cv_final(const DevBatch& b, const CvArgs& a, hipStream_t s);
 void launch_lbfgs(const LbArgs& a, const DevBatch& db, int init, hipStream_t s);  // gprx_lbfgs.hip
 void launch_lbfgs_final(const LbArgs& a, const DevBatch& db, hipStream_t s);
 

@@ -1152,3 +1152,5 @@ void launch_pred_final(const DevBatch& b, hipStream_t s) {
 #include "gprx_loo.h"
 // ... and the gradient of their log predictive probability.
 #include "gprx_loograd.h"
+// ... and k-fold cross-validation.
+#include "gprx_cvfold.h"

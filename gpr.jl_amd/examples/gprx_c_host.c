@@ -12,6 +12,8 @@
  *                                                                        opt_theta0 (slot 0)
  *   the same with the leave-one-out objective (gprx_batch_optimize_obj,
  *   GPRX_OBJ_LOO: minimises -logp_LOO), from the same start:             loo_min, loo_evals
+ *   5-fold cross-validation (point i in fold i mod 5) at those minimisers
+ *   (gprx_batch_set_folds, gprx_batch_cvfold):                           cv_logp
  * Exit status 0 on success; on failure the gprx status string goes to stderr.
  */
 #include <stdint.h>
@@ -132,6 +134,15 @@ int main(int argc, char** argv) {
   for (int g = 0; g < G; ++g) ev[g] = fc[g];
   print_row("loo_min", fmin, G);
   print_row("loo_evals", ev, G);
+  /* ... and logp_CVfold over 5 folds from the factorisation the optimiser's refit left */
+  int* fold_of = (int*)malloc((size_t)N * sizeof(int));
+  for (int i = 0; i < N; ++i) fold_of[i] = i % 5;
+  rc = gprx_batch_set_folds(b, fold_of, 0, 5);
+  if (rc) return fail("gprx_batch_set_folds", rc, ctx);
+  rc = gprx_batch_cvfold(b, NULL, NULL, NULL, fmin, NULL);
+  if (rc) return fail("gprx_batch_cvfold", rc, ctx);
+  print_row("cv_logp", fmin, G);
+  free(fold_of);
   free(thx);
   free(fmin);
   free(fc);

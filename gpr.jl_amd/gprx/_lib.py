@@ -43,6 +43,7 @@ STOP_CONVERGED = 0x100
 # gprx_batch_optimize_obj: GPRX_OBJ_MLL, GPRX_OBJ_LOO
 OBJ_MLL = 0
 OBJ_LOO = 1
+CVFOLD_MAX = 1024  # GPRX_CVFOLD_MAX
 
 
 class OptOptions(C.Structure):
@@ -87,6 +88,8 @@ SIGNATURES = {
     "gprx_batch_cov_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "gprx_batch_loo": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),
     "gprx_batch_loo_grad": (C.c_int, [_vp, _dp, _dp, _ip]),
+    "gprx_batch_set_folds": (C.c_int, [_vp, _ip, C.c_size_t, C.c_int]),
+    "gprx_batch_cvfold": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),
     "gprx_opt_defaults": (None, [C.POINTER(OptOptions)]),
     "gprx_batch_optimize": (C.c_int, [_vp, _dp, C.POINTER(OptOptions), _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "gprx_batch_optimize_obj": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(OptOptions), _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
@@ -100,6 +103,8 @@ SIGNATURES = {
     "gprx_gp_sample": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "gprx_gp_loo": (C.c_int, [_vp, _dp, _dp, _dp]),
     "gprx_gp_loo_grad": (C.c_int, [_vp, _dp, _dp]),
+    "gprx_gp_set_folds": (C.c_int, [_vp, _ip, C.c_int]),
+    "gprx_gp_cvfold": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "gprx_gp_batch": (_vp, [_vp]),
     "gprx_rollout_min": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(_vp), _ip, C.c_int,
                                    _ip, _dp, _dp]),
@@ -162,6 +167,7 @@ def _load():
 BUILD_SOURCES = ["csrc/gprx_kernels.hip", "csrc/gprx_lbfgs.hip", "csrc/gprx_projection.hip", "csrc/gprx_api.hip",
                  "csrc/gprx_internal.h", "csrc/gprx_device.h", "csrc/gprx_cores.h", "csrc/gprx_stamps.h",
                  "csrc/gprx_gemm.h", "csrc/gprx_factor.h", "csrc/gprx_predcov.h", "csrc/gprx_loo.h", "csrc/gprx_loograd.h",
+                 "csrc/gprx_cvfold.h",
                  "../include/gprx.h"]
 
 

@@ -349,6 +349,39 @@ class GPBatch:
             L.check(rc, self.ctx.h)
         return dict(logp=lp, grad=gr, status=st)
 
+    def set_folds(self, fold_of, nfolds: int | None = None):
+        """The folds of cvfold(): fold_of is an (N,) int array shared by the slots or (B, N), the fold
+        id 0..nfolds-1 of every training point (nfolds: the largest id + 1 unless given; an empty
+        fold is allowed).  Any partition; a fold holds at most L.CVFOLD_MAX points."""
+        fo = np.ascontiguousarray(fold_of, dtype=np.int32)
+        if fo.shape == (self.N,):
+            stride = 0
+        elif fo.shape == (self.B, self.N):
+            stride = self.N
+        else:
+            raise ValueError(f"fold_of must have shape ({self.N},) or ({self.B}, {self.N}), not {fo.shape}")
+        if nfolds is None:
+            nfolds = int(fo.max()) + 1
+        L.check(L.lib.gprx_batch_set_folds(self.h, L.iptr(fo), stride, int(nfolds)), self.ctx.h)
+        self.nfolds = int(nfolds)
+
+    def cvfold(self, raise_on_error: bool = False):
+        """k-fold cross-validation from the last factorisation over set_folds()'s folds [ext
+        predict_CVfold(gp, folds), logp_CVfold(gp, folds)]: dict(mu[B,N], var[B,N], logp_fold[B,F],
+        logp[B], status[B]).  mu is in the space of the targets given to set_train; var is the y-space
+        marginal variance of a point given the other folds.  NaN rows for the slots that failed in that
+        evaluation, and at the points of a fold whose block is not positive definite (status 1); a
+        status raises only with raise_on_error (as run)."""
+        F = getattr(self, "nfolds", 0)
+        mu, var = (np.empty((self.B, self.N)) for _ in range(2))
+        lpf = np.empty((self.B, max(F, 1)))
+        lp = np.empty(self.B)
+        st = np.empty(self.B, dtype=np.int32)
+        rc = L.lib.gprx_batch_cvfold(self.h, L.dptr(mu), L.dptr(var), L.dptr(lpf), L.dptr(lp), L.iptr(st))
+        if rc not in (L.OK, L.NOT_POSITIVE_DEFINITE, L.INVALID_ARGUMENT) or (raise_on_error and rc != L.OK):
+            L.check(rc, self.ctx.h)
+        return dict(mu=mu, var=var, logp_fold=lpf, logp=lp, status=st)
+
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):  # a closed context already synchronised its stream

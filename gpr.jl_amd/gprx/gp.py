@@ -249,6 +249,25 @@ class GPE:
         [ext, recalled: dlogpdθ_LOO(gp)]; the prior mean has no parameters here."""
         return self._batch.loo_grad(raise_on_error=True)["grad"][0].copy()
 
+    def _set_folds(self, folds):
+        fo = folds_to_ids(folds, self._batch.N)
+        self._batch.set_folds(fo, nfolds=len(folds))
+
+    def predict_CVfold(self, folds):
+        """(μ_i, σ²_i) of every training point predicted from the points outside its fold [ext
+        predict_CVfold(gp, folds)], from the last factorisation.  folds: a list of index vectors
+        (0-based) that partition the training points; overlapping or non-covering folds raise
+        ValueError.  The prior mean at x is added back here; σ² is the y-space marginal variance (the
+        folds' full covariances are not returned)."""
+        self._set_folds(folds)
+        r = self._batch.cvfold(raise_on_error=True)
+        return r["mu"][0] + self._mu, r["var"][0].copy()
+
+    def logp_CVfold(self, folds) -> float:
+        """Sum over the folds of log p(y_V | y_-V) [ext logp_CVfold(gp, folds)]."""
+        self._set_folds(folds)
+        return float(self._batch.cvfold(raise_on_error=True)["logp"][0])
+
     def predict_y_mean(self, xs):
         """predict_y(gp, obs)[1] without the variance: the rollout call of
         examples/utils/predictdynamics.jl:13 (uses the mean only); skips the O(N^2 M) variance."""
@@ -260,6 +279,26 @@ class GPE:
         self._batch.set_test(xs)
         mu, _ = self._batch.predict(variance=False)
         return mu[0] + self.mean.mean(xs)
+
+
+def folds_to_ids(folds, N: int) -> np.ndarray:
+    """GaussianProcesses' folds argument, a list of index vectors (0-based here), as the fold id of
+    every point.  ValueError unless the folds partition 0..N-1 (an empty fold is allowed)."""
+    fo = np.full(int(N), -1, dtype=np.int32)
+    for f, idx in enumerate(folds):
+        idx = np.asarray(idx)
+        if idx.size == 0:
+            continue
+        if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"fold {f}: an index vector of integers is needed")
+        if idx.min() < 0 or idx.max() >= N:
+            raise ValueError(f"fold {f}: index out of range 0..{N - 1}")
+        if np.unique(idx).size != idx.size or np.any(fo[idx] >= 0):
+            raise ValueError(f"fold {f} overlaps itself or an earlier fold")
+        fo[idx] = f
+    if len(folds) < 1 or np.any(fo < 0):
+        raise ValueError("the folds do not cover every training point")
+    return fo
 
 
 def GP(x, y, mean, kernel, logNoise: float = -2.0, ctx: Context | None = None) -> GPE:
@@ -289,3 +328,11 @@ def logp_LOO(gp: GPE) -> float:
 
 def dlogpdtheta_LOO(gp: GPE) -> np.ndarray:
     return gp.dlogpdtheta_LOO()
+
+
+def predict_CVfold(gp: GPE, folds):
+    return gp.predict_CVfold(folds)
+
+
+def logp_CVfold(gp: GPE, folds) -> float:
+    return gp.logp_CVfold(folds)

@@ -102,12 +102,14 @@ def local_trials(exp: str, N: int, trial_ids, testsamples: int) -> list[dict]:
 
 def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
                      max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
-                     loo: bool = False, objective: str = "mll") -> dict:
+                     loo: bool = False, objective: str = "mll", cv_folds=None) -> dict:
     """One (experiment, N) of parallelsearch for this rank's trials (sweep.run_group on the
     search's inputs).  Adds the per-trial raw start params (n_local, d+1).  loo: also loo_logp
     (n_local, G), logp_LOO of every GP at its minimiser (sweep.run_group); recorded, not used.
     objective: "mll" (the default, unchanged) or "loo": the GPs minimise -logp_LOO on the device
-    optimiser (GPBatch.optimize(objective="loo")); the result's keys are the same."""
+    optimiser (GPBatch.optimize(objective="loo")); the result's keys are the same.
+    cv_folds: an integer K also records cv_logp (n_local, G), the K-fold logp_CVfold (point i in fold
+    i mod K) of every GP at its minimiser (sweep.run_group); None: nothing changes."""
     from .sweep import run_group
 
     mech, coords = split(exp)
@@ -115,7 +117,8 @@ def run_search_group(exp: str, N: int, trial_ids, ctx, testsamples: int = 100, s
     if not trials:
         return {}
     r = run_group(mech, N, "max" if coords == "MAX" else "min", [t["trial"] for t in trials], ctx, testsamples,
-                  simsteps, max_evals, time_limit, keep=keep, trials=trials, loo=loo, objective=objective)
+                  simsteps, max_evals, time_limit, keep=keep, trials=trials, loo=loo, objective=objective,
+                  cv_folds=cv_folds)
     r["params"] = np.stack([t["params"] for t in trials])
     return r
 
@@ -142,11 +145,12 @@ def _dist():
 
 def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
         max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None, loo: bool = False,
-        objective: str = "mll") -> dict:
+        objective: str = "mll", cv=None) -> dict:
     """hyperparameter.jl's loop (N outer, experiments inner).  Every rank runs its trials of every
     group; rank 0 returns the gathered params_final checkpoint (other ranks None).  Without an
     initialised process group: one rank.  loo: every entry of the checkpoint also lists loo_logp, one
-    row of G values per kept trial; createconfig still selects by kstep_mse."""
+    row of G values per kept trial; createconfig still selects by kstep_mse.  cv: an integer K lists
+    cv_logp (run_search_group's cv_folds) the same way; None: the checkpoint is what it was."""
     from .batch import Context
 
     dist = _dist()
@@ -162,7 +166,8 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
         for exp in experiments:
             mech, coords = split(exp)
             d = 13 * data.NBODIES[mech] if coords == "MAX" else 2 * len(data.MIN_COORDS[mech])
-            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit, loo=loo, objective=objective)
+            r = run_search_group(exp, N, mine, ctx, testsamples, simsteps, max_evals, time_limit, loo=loo, objective=objective,
+                                 cv_folds=cv)
             G = len(data.VW_INDICES[mech]) if coords == "MAX" else len(data.MIN_COORDS[mech])
             n = len(mine)
             nb = int(r.get("batches", 1 if r else 0))
@@ -174,6 +179,8 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
             keys = ("kstep_mse", "failed", "params", "t")
             if loo:
                 local["loo_logp"], width["loo_logp"], keys = r.get("loo_logp", np.zeros((0, G))), G, keys + ("loo_logp",)
+            if cv is not None:
+                local["cv_logp"], width["cv_logp"], keys = r.get("cv_logp", np.zeros((0, G))), G, keys + ("cv_logp",)
             local = {k: np.asarray(v, dtype=np.float64).reshape(n, width.get(k, 1)) for k, v in local.items()}
             if dist:
                 g = shard.gather_results(local, n_trials, lambda q: shard.shard_trials(n_trials, q, world), 0,
@@ -189,6 +196,8 @@ def run(experiments=EXPERIMENTS, sizes=SIZES, n_trials: int = 100, testsamples: 
                                           "dropped": int((~keep).sum())}
                 if loo:
                     results["params"][key]["loo_logp"] = [[float(x) for x in row] for row in g["loo_logp"][keep]]
+                if cv is not None:
+                    results["params"][key]["cv_logp"] = [[float(x) for x in row] for row in g["cv_logp"][keep]]
                 timing[key] = {"seconds_max_rank": float(np.max(g["t"][:, 0])) if n_trials else 0.0,
                                "device_batches_rank0": nb,
                                "gp_fits": n_trials * (len(data.VW_INDICES[mech]) if coords == "MAX"
@@ -217,6 +226,8 @@ def main(argv=None):
     ap.add_argument("--loo", action="store_true", help="record logp_LOO of every GP at its minimiser (loo_logp)")
     ap.add_argument("--objective", choices=("mll", "loo"), default="mll",
                     help="what every GP's optimiser minimises on the device LBFGS: -mll or -logp_LOO")
+    ap.add_argument("--cv", type=int, default=None, metavar="K",
+                    help="record the K-fold logp_CVfold of every GP at its minimiser (cv_logp; point i in fold i mod K)")
     ap.add_argument("--out", default="gpurun_out/params_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -233,7 +244,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = run([e for e in a.experiments.split(",") if e], [int(s) for s in a.sizes.split(",") if s], a.trials,
               a.testsamples, a.simsteps, a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True), loo=a.loo, objective=a.objective)
+              log=lambda s: print(s, flush=True), loo=a.loo, objective=a.objective, cv=a.cv)
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

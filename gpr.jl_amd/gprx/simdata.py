@@ -380,3 +380,16 @@ def trial_from_dataset(mech: str, ds: dict, N: int, M: int = 100, seed: int = 0,
     X, Xcurr = old.T.copy(), cur.T.copy()
     Y = np.stack([Xcurr[i - 1, :] for i in idx], axis=0)
     return dict(X=X, Xcurr=Xcurr, Y=Y, Xs=told.T.copy() if M > 0 else None, idx=idx, d=X.shape[0], truth=truth)
+
+
+def trial_folds(ds: dict, N: int, seed: int = 0) -> np.ndarray:
+    """The trajectory index (N,) of each training row that trial_from_dataset(mech, ds, N, seed=seed)
+    keeps: its permutation of the training rows, and row // plan(config)["train_samples"], since
+    generate_dataset appends the rows trajectory by trajectory.  The folds of leave-one-trajectory-out
+    cross-validation (GPBatch.set_folds; ids that no kept row carries are empty folds)."""
+    rng = np.random.default_rng(seed)
+    ntr = ds["train_old"].shape[0]
+    if N > ntr:
+        raise ValueError(f"the dataset holds {ntr} training rows; asked for {N}")
+    itr = rng.permutation(ntr)[:N]
+    return (itr // plan(ds["config"])["train_samples"]).astype(np.int32)

@@ -138,7 +138,7 @@ def local_trials(mech: str, N: int, variant: str, trial_ids, testsamples: int, c
 def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int = 100, simsteps: int = 20,
               max_evals: int | None = 30, time_limit: float = float("nan"), keep: bool = False,
               trials: list | None = None, budget: int | None = None, md_rollout: str = "stepwise", dataset=None,
-              loo: bool = False, objective: str = "mll") -> dict:
+              loo: bool = False, objective: str = "mll", cv_folds=None) -> dict:
     """One (mechanism, N, variant) group for this rank's trials: device optimise of every GP,
     then the variant's evaluation.  Returns per-trial arrays (n_local, ...) and timings.
     trials: prebuilt local_trials-shaped inputs (the hyper-parameter search's), else noise.jl's.
@@ -154,7 +154,12 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     nothing selects by it.  Off: the result is what it was, key for key.
     objective: what the optimiser minimises -- "mll" (the default: -mll on the device state machine, as
     ever) or "loo" (-logp_LOO on the same state machine, GPBatch.optimize(objective="loo")); the result's keys
-    are the same."""
+    are the same.
+    cv_folds: also return cv_logp (n_local, G), the k-fold logp_CVfold of every GP at its minimiser
+    (GPBatch.cvfold right after the optimiser's refit, in every device batch; NaN where the refit or a
+    fold's block failed), recorded like loo_logp.  An integer K: point i is in fold i mod K;
+    "trajectory": leave-one-trajectory-out, the folds of simdata.trial_folds (needs `dataset`).  None
+    (the default): the result is what it was, key for key."""
     if md_rollout not in MD_ROLLOUTS:
         raise ValueError(f"md_rollout must be one of {MD_ROLLOUTS}, not {md_rollout!r}")
     if trials is None:
@@ -162,6 +167,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     n = len(trials)
     if n == 0:
         return {}
+    folds = cv_fold_ids(mech, N, trials, cv_folds, dataset)
     plan = shard.group_plan(trials, ctx, budget)
     if keep and len(plan) > 1:
         raise ValueError(f"run_group(keep=True): the group needs {len(plan)} device batches")
@@ -169,7 +175,7 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     for lo, hi, nd in plan:
         rb = shard.RankBatch(trials[lo:hi], ctx=ctx, dev_trials=nd)
         part = _run_chunk(mech, variant, trials[lo:hi], rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout, loo,
-                          objective)
+                          objective, None if folds is None else folds[lo:hi])
         if keep:
             part.update(rb=rb, trials=trials)
         else:
@@ -178,14 +184,37 @@ def run_group(mech: str, N: int, variant: str, trial_ids, ctx, testsamples: int 
     if len(parts) == 1:
         return parts[0]
     out = {k: np.concatenate([p[k] for p in parts]) for k in ("kstep_mse", "projectionerror", "failed", "mll", "theta",
-                                                              "status", "f_calls") + (("loo_logp",) if loo else ())}
+                                                              "status", "f_calls") + (("loo_logp",) if loo else ())
+           + (("cv_logp",) if folds is not None else ())}
     out.update(rounds=sum(p["rounds"] for p in parts), t_opt=sum(p["t_opt"] for p in parts),
                t_eval=sum(p["t_eval"] for p in parts), slots=sum(p["slots"] for p in parts), batches=len(parts))
     return out
 
 
+def cv_fold_ids(mech, N, trials, cv_folds, dataset=None):
+    """run_group's cv_folds as one fold-id row (N,) per trial, or None."""
+    if cv_folds is None:
+        return None
+    if cv_folds == "trajectory":
+        if dataset is None:
+            raise ValueError('cv_folds="trajectory" needs the trials of a dataset')
+        from . import simdata
+
+        return [simdata.trial_folds(_dataset_of(dataset, t["trial"]), N, seed=t["seed"]) for t in trials]
+    if isinstance(cv_folds, (int, np.integer)) and not isinstance(cv_folds, bool) and cv_folds >= 1:
+        return [(np.arange(N) % int(cv_folds)).astype(np.int32)] * len(trials)
+    raise ValueError(f'cv_folds must be None, an integer K >= 1 or "trajectory", not {cv_folds!r}')
+
+
+def _cv_logp(rb, folds, status):
+    """cv_logp (n, G) of the batch rb at its factorisation; the padding trials take the last one's folds."""
+    rows = list(folds) + [folds[-1]] * (rb.n_dev - rb.n)
+    rb.batch.set_folds(np.repeat(np.stack(rows), rb.G, axis=0), nfolds=int(max(r.max() for r in rows)) + 1)
+    return np.where(status == 0, rb._shape(rb.batch.cvfold()["logp"]), np.nan)
+
+
 def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout="stepwise", loo=False,
-               objective="mll") -> dict:
+               objective="mll", folds=None) -> dict:
     """run_group's work for the trials of one device batch rb."""
     from .optim import LBFGS, Options
 
@@ -200,6 +229,7 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
     G = rb.G
     # the batch is factorised at the minimisers (rb.optimize's closing evaluation)
     loo_logp = np.where(opt["status"] == 0, rb._shape(rb.batch.loo()["logp"]), np.nan) if loo else None
+    cv_logp = _cv_logp(rb, folds, opt["status"]) if folds is not None else None
     ok_gp = opt["status"] == 0  # (n, G)
     ok_gp &= np.array([[not t.get("vi_failed", False)] for t in trials])  # MeanDynamics mean failed: dropped
     err = np.full(n, math.inf)
@@ -274,6 +304,8 @@ def _run_chunk(mech, variant, trials, rb, ctx, testsamples, simsteps, max_evals,
                slots=n * G, batches=1)
     if loo:
         out["loo_logp"] = loo_logp
+    if folds is not None:
+        out["cv_logp"] = cv_logp
     return out
 
 
@@ -316,11 +348,13 @@ def run_vi_baseline(mech: str, trial_ids, testsamples: int = 100, simsteps: int 
 
 def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsamples: int = 100, simsteps: int = 20,
         max_evals: int | None = 30, time_limit: float = float("nan"), ctx=None, log=None,
-        md_rollout: str = "stepwise", dataset=None) -> dict:
+        md_rollout: str = "stepwise", dataset=None, cv=None) -> dict:
     """The sweep.  Every rank runs its trials of every group; rank 0 returns the gathered
     checkpoint dict (other ranks None).  Without an initialised process group: one rank.
     dataset: a directory of simulated datasets (gprx.simdata.load_datasets) instead of the synthetic
-    generator."""
+    generator.
+    cv: run_group's cv_folds ("trajectory" with a dataset, or an integer K); every group's entry then
+    also lists cv_logp, one row of G values per kept trial.  None: the checkpoint is what it was."""
     from .batch import Context
 
     dist = _dist()
@@ -364,15 +398,20 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
                 if var == "vi":
                     continue
                 r = run_group(mech, N, var, mine, ctx, testsamples, simsteps, max_evals, time_limit, md_rollout=md_rollout,
-                              dataset=dsets)
+                              dataset=dsets, cv_folds=cv)
                 local = {"kstep_mse": r.get("kstep_mse", np.zeros(0)), "perr": r.get("projectionerror", np.zeros(0)),
                          "failed": r.get("failed", np.zeros(0, dtype=bool)).astype(np.float64),
                          "ok": np.all(r["status"] == 0, axis=1).astype(np.float64) if r else np.zeros(0),
                          "t": np.full(len(mine), r.get("t_opt", 0.0) + r.get("t_eval", 0.0))}
+                keys = ("kstep_mse", "perr", "failed", "ok", "t")
+                if cv is not None:  # one gathered column per output GP
+                    G = len(data.VW_INDICES[mech]) if var.endswith("max") else NCOORD[mech]
+                    cvl = r.get("cv_logp", np.zeros((0, G)))
+                    local.update({f"cv{g_}": cvl[:, g_] for g_ in range(G)})
+                    keys += tuple(f"cv{g_}" for g_ in range(G))
                 if dist:
                     g = shard.gather_results({k: v.reshape(-1, 1) for k, v in local.items()}, n_trials,
-                                             lambda q: shard.shard_trials(n_trials, q, world), 0,
-                                             keys=("kstep_mse", "perr", "failed", "ok", "t"))
+                                             lambda q: shard.shard_trials(n_trials, q, world), 0, keys=keys)
                 else:
                     g = {k: v.reshape(-1, 1) for k, v in local.items()}
                 key = f"{mech}_{'MAX' if var.endswith('max') else 'MIN'}{N}"
@@ -387,6 +426,9 @@ def run(mechs=MECHS, sizes=SIZES, variants=VARIANTS, n_trials: int = 100, testsa
                                                        "projectionerror": [float(v) for v in g["perr"][keep, 0]],
                                                        "variant": var, "ok": int(g["ok"][:, 0].sum()),
                                                        "dropped": int((~keep).sum()), "parity": PARITY[var]}
+                    if cv is not None:
+                        results[et][key]["cv_logp"] = [[float(g[f"cv{g_}"][i, 0]) for g_ in range(G)]
+                                                       for i in np.flatnonzero(keep)]
                     timing[f"{key}/{var}"] = {"seconds_max_rank": float(np.max(g["t"][:, 0])) if n_trials else 0.0,
                                               "gp_fits": n_trials * (len(data.VW_INDICES[mech]) if var.endswith("max")
                                                                      else NCOORD[mech])}
@@ -417,6 +459,9 @@ def main(argv=None):
     ap.add_argument("--dataset", default=None,
                     help="directory of simulated datasets (gprx.simdata.write_dataset: DIR/<mech>[/<k>]) instead of "
                          "the synthetic generator; the vi, max and md_max variants")
+    ap.add_argument("--cv", default=None,
+                    help='also record cv_logp, the k-fold logp_CVfold of every GP at its minimiser: "trajectory" '
+                         "(leave-one-trajectory-out; needs --dataset) or an integer K (point i in fold i mod K)")
     ap.add_argument("--out", default="gpurun_out/sweep_final_checkpoint.json")
     ap.add_argument("--rehearse", action="store_true", help="allow ranks to share GPUs (gloo control plane)")
     ap.add_argument("--gpus", type=int, default=None,
@@ -434,7 +479,8 @@ def main(argv=None):
     res = run([m for m in a.mechs.split(",") if m], [int(s) for s in a.sizes.split(",") if s],
               [v for v in a.variants.split(",") if v], a.trials, a.testsamples, a.simsteps,
               a.max_evals if a.max_evals > 0 else None, a.time_limit,
-              log=lambda s: print(s, flush=True), md_rollout=a.md_rollout, dataset=a.dataset)
+              log=lambda s: print(s, flush=True), md_rollout=a.md_rollout, dataset=a.dataset,
+              cv=None if a.cv is None else (a.cv if a.cv == "trajectory" else int(a.cv)))
     wall = time.perf_counter() - t0
     if res is not None:
         res["wall_seconds"] = wall

@@ -12,6 +12,7 @@ experiment scripts (examples/noise.jl, examples/hyperparameter.jl) stay textuall
     rand(gp, x*, n)                       -> gprx_gp_sample (randn on the Julia side)
     predict_LOO(gp), logp_LOO(gp)         -> gprx_gp_loo
     dlogpdθ_LOO(gp)                       -> gprx_gp_loo_grad   [ext, recalled]
+    predict_CVfold(gp, folds), logp_CVfold(gp, folds) -> gprx_gp_set_folds, gprx_gp_cvfold
 
 plus `GPRx.optimize_all!(gps)`: the loop `for gp in gps; optimize!(gp, LBFGS(linesearch =
 BackTracking(order=2)), Optim.Options(time_limit=10.)); end` of CPnoise.jl:37-43 as ONE
@@ -201,6 +202,44 @@ function GaussianProcesses.dlogpdθ_LOO(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd})
     check(ccall((:gprx_gp_loo_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
                 handle(gp).ptr, C_NULL, g), gp)
     return g
+end
+# predict_CVfold(gp, folds), logp_CVfold(gp, folds) (GaussianProcesses crossvalidation.jl): folds is a
+# vector of 1-based index vectors that partition the training points.  Every fold's points are
+# predicted jointly from the points outside it, from the device factorisation of the last evaluation
+# (gprx_gp_set_folds / gprx_gp_cvfold: R&W 5.4.2 in block form over the folds' blocks of K^-1).
+# Returns the mean (prior mean added back) and the y-space marginal variance of every point in the
+# order of the training points, and the sum of the folds' log predictive probabilities.  Methods of
+# GaussianProcesses' own functions, like predict_LOO above, so a script's predict_CVfold(gp, folds)
+# reaches the device unchanged [ext, recalled: the names are crossvalidation.jl's; the package source
+# was not available to confirm its return shapes].
+function fold_ids(folds::AbstractVector{<:AbstractVector{<:Integer}}, N::Integer)
+    ids = fill(Cint(-1), N)
+    for (f, idx) in enumerate(folds), i in idx
+        1 <= i <= N || throw(ArgumentError("fold $f: index $i out of range 1:$N"))
+        ids[i] < 0 || throw(ArgumentError("fold $f overlaps an earlier fold at point $i"))
+        ids[i] = Cint(f - 1)
+    end
+    all(>=(0), ids) || throw(ArgumentError("the folds do not cover every training point"))
+    return ids
+end
+function set_folds!(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, folds)
+    ids = fold_ids(folds, length(gp.y))
+    check(ccall((:gprx_gp_set_folds, LIB), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint), handle(gp).ptr, ids, length(folds)), gp)
+end
+function GaussianProcesses.predict_CVfold(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, folds)
+    set_folds!(gp, folds)
+    N = length(gp.y)
+    mu, var = zeros(N), zeros(N)
+    check(ccall((:gprx_gp_cvfold, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                handle(gp).ptr, mu, var, C_NULL, C_NULL), gp)
+    return mu .+ GaussianProcesses.mean(gp.mean, Matrix{Float64}(gp.x)), var
+end
+function GaussianProcesses.logp_CVfold(gp::GPE{<:Any,<:Any,<:Mean,<:SEArd}, folds)
+    set_folds!(gp, folds)
+    lp = Ref{Float64}(0.0)
+    check(ccall((:gprx_gp_cvfold, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                handle(gp).ptr, C_NULL, C_NULL, C_NULL, lp), gp)
+    return lp[]
 end
 function loo_grad_batch(batch::Ptr{Cvoid}, B::Integer, d::Integer)
     logp, grad, status = zeros(B), zeros(d + 2, B), zeros(Cint, B)

@@ -17,6 +17,7 @@
  *                      every GPE (CPnoise.jl:40); the reference's scripts use the mean only
  *   gprx_gp_loo / gprx_batch_loo   [ext] predict_LOO(gp), logp_LOO(gp) (crossvalidation.jl), on every GPE
  *   gprx_gp_loo_grad / gprx_batch_loo_grad   [ext, recalled] dlogpdtheta_LOO(gp) (crossvalidation.jl)
+ *   gprx_gp_cvfold / gprx_batch_cvfold   [ext] predict_CVfold(gp, folds), logp_CVfold(gp, folds) (crossvalidation.jl)
  *   gprx_rollout_min   predictdynamicsmin             examples/utils/predictdynamics.jl:30-102
  *   gprx_batch_*       the G per-output GPs of a trial (CPnoise.jl:37-43) and the trial loop
  *                      (examples/parallel/core.jl:28) evaluated as one device batch
@@ -38,6 +39,7 @@
 #ifndef GPRX_H
 #define GPRX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -241,6 +243,55 @@ int gprx_batch_loo(gprx_batch* batch, double* mu, double* var, double* logp_i, d
  * "loo_diag", "loo_final", "loo_kinv", "loo_beta", "loo_grad", "loo_grad_final").                 */
 int gprx_batch_loo_grad(gprx_batch* batch, double* logp, double* grad, int* status);
 
+/* ---- k-fold cross-validation ---------------------------------------------------------------- */
+/* [ext] predict_CVfold(gp, folds) and logp_CVfold(gp, folds) of GaussianProcesses' crossvalidation.jl:
+ * the joint prediction of every fold's points from the points of the other folds and its log
+ * predictive probability, from the factorisation of the last evaluation (no refit).  For a fold V of
+ * m points, Q = [K^-1]_VV and a = alpha_V (K carries exp(2 log sn) + eps; alpha = K^-1 y, y the targets
+ * given to set_train), Rasmussen & Williams 5.4.2 in block form:
+ *   Sigma_V = Q^-1,  mu_V = y_V - Q^-1 a,  logp_V = -a^T Q^-1 a / 2 + log|Q| / 2 - m log(2 pi) / 2
+ * computed with Q = C C^T, w = C^-1 a as
+ *   logp_V = -|w|^2 / 2 + sum_i log C_ii - m log(2 pi) / 2,  mu_V = y_V - C^-T w,  var_i = sum_k (C^-1)_ki^2.
+ * Folds of one point each give gprx_batch_loo; one fold of all points gives logp = mll.
+ *
+ * gprx_batch_set_folds: fold_of[N] is the fold id, 0..nfolds-1, of every training point; slot_stride
+ * as in gprx_batch_set_train (0: one array shared by all slots, N: one per slot).  The folds are any
+ * partition of the points (not contiguous, not equal in size; an empty fold contributes 0 to logp).
+ * GPRX_INVALID_ARGUMENT for a NULL argument, a stride other than 0 or N, nfolds < 1, an id out of
+ * range or a fold of more than GPRX_CVFOLD_MAX points (one workgroup factors one fold's block, as in
+ * gprx_batch_sample).  The call orders each slot's points by fold (stably), builds the fold starts and
+ * the table of the 64 x 64 tiles of K^-1 that a fold reaches, and uploads them once; they stay with
+ * the batch until the next gprx_batch_set_folds.  It needs no training data and no factorisation.
+ * A call that fails (GPRX_OUT_OF_MEMORY for the table included) leaves the batch's folds as they were.
+ *
+ * gprx_batch_cvfold: host outputs, any may be NULL: mu[B*N] and var[B*N] in the order of the training
+ * points (var the y-space marginal variances diag(Sigma_V)), logp_fold[B*nfolds], logp[B] (the sum of
+ * the folds' in ascending fold order), status[B].  GPRX_NOT_READY before a successful factorisation
+ * or before gprx_batch_set_folds.  A slot whose status in that evaluation was not GPRX_OK gets NaN in
+ * all its outputs and keeps that status; the other slots are unaffected.  A fold whose block Q has a
+ * pivot that is not finite or <= 0 (no jitter is added: Q is a principal block of K^-1) gives its slot
+ * GPRX_NOT_POSITIVE_DEFINITE and NaN at that fold's points, in that fold's logp and in the slot's logp.
+ * Returns GPRX_OK or the first failing slot's status.  The results are bitwise reproducible and depend
+ * on N, the fold layout and the index alone: not on B or on the slot's place in the batch.
+ * Accuracy: Q is as well conditioned as K, but mu and var of a fold go through Q^-1 = C^-T C^-1 after
+ * K^-1 was formed, and lose about cond(K)^2 eps for a fold that holds most of the points (for one fold
+ * of all points var_i = K_ii is recovered from K^-1: at cond(K) = 1e11 its error is of the order of
+ * var itself, with status GPRX_OK).  Small folds at such theta and every fold at moderate cond(K) are
+ * accurate to the usual cond(K) eps; logp and logp_fold are well behaved throughout (one fold: mll).
+ * No fp64 closed form from K^-1 does better; where the variances of large folds at ill-conditioned
+ * theta matter, refit without the fold.
+ * The call overwrites the factorisation workspace Lw (with L^-T's rows in fold order, then fold by
+ * fold with C and C^-T), which nothing reads before the next evaluation rewrites it: predictions,
+ * alpha, gprx_batch_loo and gprx_batch_loo_grad after it return what they return without it.  The
+ * rest comes from the context's scratch buffer: 8 B (4096 T + 4 Npad + nfolds + 1) + 4 B (nfolds + 1)
+ * bytes, T the largest number of tiles a slot's folds reach (nt for folds within a tile, nt (nt + 1) / 2
+ * at most); GPRX_OUT_OF_MEMORY if it cannot be had.  gprx_batch_bytes and gprx_batch_cov_bytes are
+ * unchanged.  The launches go straight on the context stream (stats "cv_pack", "cv_kinv", "cv_fold",
+ * "cv_final").                                                                                     */
+#define GPRX_CVFOLD_MAX 1024
+int gprx_batch_set_folds(gprx_batch* batch, const int* fold_of, size_t slot_stride, int nfolds);
+int gprx_batch_cvfold(gprx_batch* batch, double* mu, double* var, double* logp_fold, double* logp, int* status);
+
 /* ---- hyper-parameter optimisation on the device ------------------------------------------- */
 /* GaussianProcesses.optimize!(gp, LBFGS(linesearch=BackTracking(order=2)), Optim.Options(...))
  * (examples/maximal_coordinates/CPnoise.jl:41 and its 15 siblings) for every slot of a batch:
@@ -342,6 +393,11 @@ int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp);
 /* [ext, recalled] dlogpdtheta_LOO(gp): logp[1], grad[d+2] in the order of theta; either may be NULL
  * (gprx_batch_loo_grad on the batch of one, at the factorisation of the last lml call).         */
 int gprx_gp_loo_grad(gprx_gp* gp, double* logp, double* grad);
+/* [ext] predict_CVfold(gp, folds): mu[N], var[N]; logp_CVfold(gp, folds): logp[1], logp_fold[nfolds];
+ * any may be NULL (gprx_batch_set_folds / gprx_batch_cvfold on the batch of one, at the factorisation
+ * of the last lml call).  fold_of[N]: the fold id of every training point.                      */
+int gprx_gp_set_folds(gprx_gp* gp, const int* fold_of, int nfolds);
+int gprx_gp_cvfold(gprx_gp* gp, double* mu, double* var, double* logp_fold, double* logp);
 
 /* the single GP's underlying batch of one (slot 0), e.g. for gprx_rollout_min              */
 gprx_batch* gprx_gp_batch(gprx_gp* gp);
