@@ -116,6 +116,13 @@ int set_err(gprx_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   return code;
 }
+// A batch call's return code from its per-slot statuses: the first that is not GPRX_OK, with the
+// error text "fn: <status string>".
+int first_status(gprx_ctx* c, const char* fn, const int* st, int B) {
+  for (int s = 0; s < B; ++s)
+    if (st[s] != GPRX_OK) return set_err(c, st[s], std::string(fn) + ": " + gprx_status_string(st[s]));
+  return GPRX_OK;
+}
 
 #define HIPCHK(ctx, expr)                                                                          \
   do {                                                                                             \
@@ -921,20 +928,16 @@ int gprx_batch_run(gprx_batch* b, const double* theta, unsigned flags, double* m
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  int first = GPRX_OK;
   for (int s = 0; s < B; ++s) {
-    const int st = b->h_status[s];
-    if (status) status[s] = st;
+    if (status) status[s] = b->h_status[s];
     if (info) info[s] = b->h_status[B + s];
-    if (st != GPRX_OK && first == GPRX_OK) first = st;
     const double* o = b->h_out + (size_t)s * (d + 3);
     if (mll) mll[s] = o[0];
     if (grad && want_grad) memcpy(grad + (size_t)s * np, o + 1, np * sizeof(double));
   }
   if (want_pred) pred_out_unpack(b, mu, var, pd);
   b->factored = true;
-  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_run: ") + gprx_status_string(first));
-  return first;
+  return first_status(c, "gprx_batch_run", b->h_status, B);
 }
 
 int gprx_batch_alpha(gprx_batch* b, double* alpha) {
@@ -1067,17 +1070,15 @@ int gprx_batch_sample(gprx_batch* b, const double* Z, int S, int64_t zss, double
   HIPCHK(c, hipMemcpyAsync(hs, b->cov_st, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  int first = GPRX_OK;
   for (size_t s = 0; s < B; ++s) {
     // a slot whose evaluation failed: NaN rows (the kernels wrote them), not a failure of this call
     const bool dead = b->h_status[s] != GPRX_OK;
     if (dead) nan_fill(samples + s * S * M, (size_t)S * M);
     if (jitter) jitter[s] = dead ? NAN : hj[s];
     if (status) status[s] = dead ? b->h_status[s] : hs[s];
-    if (!dead && hs[s] != GPRX_OK && first == GPRX_OK) first = hs[s];
+    if (dead) hs[s] = GPRX_OK;
   }
-  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_sample: ") + gprx_status_string(first));
-  return first;
+  return first_status(c, "gprx_batch_sample", hs, (int)B);
 }
 
 // ---- device hyper-parameter optimisation (gprx_lbfgs.hip) ---------------------------------------
@@ -1377,7 +1378,13 @@ static int ctx_scratch(gprx_ctx* c, size_t need, char** base) {
 
 // ---- leave-one-out predictions (gprx_loo.h) ------------------------------------------------------
 // Workspace in the context scratch: kinv, mu, var, lp (B x Npad each), logp (B).  Not part of the
-// captured evaluation graphs: two launches straight on the context stream.
+// captured evaluation graphs: two launches (loo_launches) straight on the context stream.
+static void loo_launches(gprx_ctx* c, const DevBatch& db, double* kinv, double* mu, double* var, double* lp, double* logp) {
+  const double B = db.B, N = db.N, tri = N * (N + 1.0) / 2.0;
+  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, kinv, c->stream); });
+  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
+        [&] { gprx::launch_loo_final(db, kinv, mu, var, lp, logp, c->stream); });
+}
 int gprx_batch_loo(gprx_batch* b, double* mu, double* var, double* logp_i, double* logp, int* status) {
   if (!b) return GPRX_INVALID_ARGUMENT;
   gprx_ctx* c = b->ctx;
@@ -1391,10 +1398,7 @@ int gprx_batch_loo(gprx_batch* b, double* mu, double* var, double* logp_i, doubl
   if (rc) return rc;
   double* kinv = (double*)base;
   double *d_mu = kinv + rows, *d_var = d_mu + rows, *d_lp = d_var + rows, *d_logp = d_lp + rows;
-  const double B = db.B, N = db.N, tri = N * (N + 1.0) / 2.0;
-  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, kinv, c->stream); });
-  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
-        [&] { gprx::launch_loo_final(db, kinv, d_mu, d_var, d_lp, d_logp, c->stream); });
+  loo_launches(c, db, kinv, d_mu, d_var, d_lp, d_logp);
   HIPCHK(c, hipGetLastError());
   const size_t w = (size_t)db.N * sizeof(double), p = (size_t)db.Npad * sizeof(double);
   if (mu) HIPCHK(c, hipMemcpy2DAsync(mu, w, d_mu, p, w, db.B, hipMemcpyDeviceToHost, c->stream));
@@ -1405,14 +1409,8 @@ int gprx_batch_loo(gprx_batch* b, double* mu, double* var, double* logp_i, doubl
   collect(c);
   // h_status: the evaluation that factorised the batch (gprx_batch_alpha); k_loo_final wrote the
   // NaN rows of a failed slot from the same status on the device
-  int first = GPRX_OK;
-  for (int s = 0; s < db.B; ++s) {
-    const int st = b->h_status[s];
-    if (status) status[s] = st;
-    if (st != GPRX_OK && first == GPRX_OK) first = st;
-  }
-  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_loo: ") + gprx_status_string(first));
-  return first;
+  if (status) memcpy(status, b->h_status, (size_t)db.B * sizeof(int));
+  return first_status(c, "gprx_batch_loo", b->h_status, db.B);
 }
 
 int gprx_gp_loo(gprx_gp* gp, double* mu, double* var, double* logp) {
@@ -1442,10 +1440,8 @@ static LooWs loo_ws_at(char* base, const DevBatch& db) {
 // one); the caller checks hipGetLastError
 static void loo_grad_launches(gprx_ctx* c, const DevBatch& db, const LooWs& w) {
   const int d = db.d;
-  const double B = db.B, N = db.N, Np = db.Npad, tri = N * (N + 1.0) / 2.0;
-  timed(c, c->stream, "loo_diag", B * 2.0 * tri, B * 8.0 * (tri + N), [&] { gprx::launch_loo_diag(db, w.kinv, c->stream); });
-  timed(c, c->stream, "loo_final", B * 10.0 * N, B * 8.0 * 6.0 * N,
-        [&] { gprx::launch_loo_final(db, w.kinv, w.mu, w.var, w.lp, w.logp, c->stream); });
+  const double B = db.B, Np = db.Npad;
+  loo_launches(c, db, w.kinv, w.mu, w.var, w.lp, w.logp);
   timed(c, c->stream, "loo_kinv", B * (Np * Np * Np / 3.0 + 4.0 * Np * Np), B * 8.0 * (1.5 * Np * Np + 2.0 * db.nt * Np),
         [&] { gprx::launch_loo_kinv(db, w.kinv, w.bp, c->stream); });
   timed(c, c->stream, "loo_beta", B * db.nt * Np, B * 8.0 * (db.nt + 1.0) * Np, [&] { gprx::launch_loo_beta(db, w.bp, w.beta, c->stream); });
@@ -1479,14 +1475,8 @@ int gprx_batch_loo_grad(gprx_batch* b, double* logp, double* grad, int* status) 
   collect(c);
   // h_status: the evaluation that factorised the batch; k_loo_grad_final wrote the NaN rows of a
   // failed slot from the same status on the device
-  int first = GPRX_OK;
-  for (int s = 0; s < db.B; ++s) {
-    const int st = b->h_status[s];
-    if (status) status[s] = st;
-    if (st != GPRX_OK && first == GPRX_OK) first = st;
-  }
-  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_loo_grad: ") + gprx_status_string(first));
-  return first;
+  if (status) memcpy(status, b->h_status, (size_t)db.B * sizeof(int));
+  return first_status(c, "gprx_batch_loo_grad", b->h_status, db.B);
 }
 
 int gprx_gp_loo_grad(gprx_gp* gp, double* logp, double* grad) {
@@ -1628,13 +1618,8 @@ int gprx_batch_cvfold(gprx_batch* b, double* mu, double* var, double* logp_fold,
   HIPCHK(c, hipMemcpyAsync(hst.data(), a.st, (size_t)nB * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   collect(c);
-  int first = GPRX_OK;
-  for (int s = 0; s < nB; ++s) {
-    if (status) status[s] = hst[s];
-    if (hst[s] != GPRX_OK && first == GPRX_OK) first = hst[s];
-  }
-  if (first != GPRX_OK) set_err(c, first, std::string("gprx_batch_cvfold: ") + gprx_status_string(first));
-  return first;
+  if (status) memcpy(status, hst.data(), (size_t)nB * sizeof(int));
+  return first_status(c, "gprx_batch_cvfold", hst.data(), nB);
 }
 
 int gprx_gp_set_folds(gprx_gp* gp, const int* fold_of, int nfolds) {
@@ -1873,14 +1858,18 @@ struct RecReq {
   int steps_per_launch;
   double* traj;
 };
-int rec_check(gprx_ctx* c, const std::string& fn, const RecReq& q, int steps, int T) {
+// last (or null): the largest index wanted, 1 at least
+int rec_check(gprx_ctx* c, const std::string& fn, const RecReq& q, int steps, int T, int* last = nullptr) {
   if (q.R > 0 && (!q.rec || !q.traj)) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
+  int hi = 1;
   for (int t = 0; t < T; ++t)
     for (int r = 0; r < q.R; ++r) {
       const int j = q.rec[(size_t)t * q.R + r];
       if (j < 1 || j > steps + 1 || (r > 0 && j < q.rec[(size_t)t * q.R + r - 1]))
         return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": rec must be non-decreasing per trajectory, in [1, steps + 1]");
+      hi = j > hi ? j : hi;
     }
+  if (last) *last = hi;
   return GPRX_OK;
 }
 // The device buffers of a recorded call follow the one-launch call's in its RolloutIo (the records
@@ -1966,13 +1955,7 @@ int gprx_simulate(gprx_ctx* c, int mech, double dt, int steps, int T, const doub
   if (T == 0) return GPRX_OK;
   if (!start || !rec || !out) return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": null argument");
   int last = 1;  // the largest index wanted: no trajectory steps past it
-  for (int t = 0; t < T; ++t)
-    for (int r = 0; r < R; ++r) {
-      const int j = rec[(size_t)t * R + r];
-      if (j < 1 || j > steps + 1 || (r > 0 && j < rec[(size_t)t * R + r - 1]))
-        return set_err(c, GPRX_INVALID_ARGUMENT, fn + ": rec must be non-decreasing per trajectory, in [1, steps + 1]");
-      last = j > last ? j : last;
-    }
+  if (int rc = rec_check(c, fn, RecReq{R, rec, steps_per_launch, out}, steps, T, &last)) return rc;
   // The default bounds a launch whose every step runs all newton_iter = 100 iterations (a solve whose twist
   // does not settle; a stagnated one ends sooner, k_simulate): a four-bar step then takes 12 ms with 200
   // trajectories in flight (measured), 16 of them 0.19 s.  One wave per trajectory: beyond about

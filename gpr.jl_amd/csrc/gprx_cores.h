@@ -1,12 +1,8 @@
 // gprx_cores.h -- the wave-level MFMA cores (operand fragments, operand addressing, every mma_* loop)
 // and the accumulator helpers.
 //
-// gprx_kernels.hip is one translation unit cut along its banners.  It includes, in this order:
-//   gprx_device.h, gprx_cores.h, gprx_stamps.h   (before its first kernel)
-//   gprx_gemm.h, gprx_factor.h                   (after the Gram and single-tile kernels)
-//   gprx_predcov.h, gprx_loo.h, gprx_loograd.h   (last, after the launchers)
-// No other file includes them: they share the device globals and there is no relocatable device
-// code in this build.
+// A part of gprx_kernels.hip, included there once and by no other file (the parts and their order
+// are listed at its includes).
 #pragma once
 
 namespace gprx {
@@ -286,6 +282,31 @@ __device__ __forceinline__ void mma_64x64_m(d4 (&acc)[QM][QN], const double* __r
   GPRX_TRIP(MODE, 2, 3, 4, true)
   int it = 6;
   for (; it < nst; it += 2) {
+    __builtin_amdgcn_sched_barrier(0);
+    core_load<MODE, 4>(f1, pa, pb, it + 1);
+    core_mma<MODE, 4>(acc, f0);
+    core_groups<MODE>();
+    __builtin_amdgcn_sched_barrier(0);
+    const int n2 = (it + 2 < nst) ? it + 2 : nst - 1;
+    core_load<MODE, 4>(f0, pa, pb, n2);
+    core_mma<MODE, 4>(acc, f1);
+    core_groups<MODE>();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+// k_loo_grad's and k_cv_kinv's core: the plain 64 x 64 product over whole 64-tiles of K, operands
+// through global addresses; SAME: B = A, a diagonal tile, which forms its blocks b <= a only
+template <bool SAME>
+__device__ __forceinline__ void mma_64x64_sq(d4 (&acc)[QM][QN], const double* __restrict__ A, size_t lda,
+                                             const double* __restrict__ B, size_t ldb, int K) {
+  constexpr int MODE = SAME ? TRI_AB_FIRST : PLAIN;  // trip 4: the dense masks (SAME: B = A, blocks b <= a)
+  const int nst = __builtin_amdgcn_readfirstlane(K / (4 * Q4SD));  // even: K is whole 64-tiles
+  if (nst <= 0) return;
+  const CorePtrG pa = core_ptr_g(A, lda), pb = core_ptr_g(B, ldb);
+  Frag4 f0, f1;
+  core_load<MODE, 4>(f0, pa, pb, 0);
+  for (int it = 0; it < nst; it += 2) {
     __builtin_amdgcn_sched_barrier(0);
     core_load<MODE, 4>(f1, pa, pb, it + 1);
     core_mma<MODE, 4>(acc, f0);

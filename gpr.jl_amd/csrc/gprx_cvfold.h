@@ -22,7 +22,8 @@
 // No atomics, no spinning; every workgroup barrier is in workgroup-uniform control flow; every
 // reduction order depends on (N, the fold layout, index) alone, not on B, the slot or the block.
 //
-// Included last by gprx_kernels.hip (see gprx_loo.h for the order of the parts).
+// A part of gprx_kernels.hip, included there last and by no other file (the parts and their order
+// are listed at its includes).
 #pragma once
 
 namespace gprx {
@@ -301,13 +302,10 @@ __global__ __launch_bounds__(NTHR) void k_cv_fold(DevBatch db, CvArgs a) {
 // ============================================================================================
 // cv_final: mu_i = y_i - r, var_i back in point order (i = perm of the packed position), and
 // logp[slot] = sum_V logp_V by k_loo_final's sum: thread t adds its folds t, t + 256, ... in ascending
-// order, then the 256 partial sums by a halving tree in LDS, every addition a two-sum with the error
-// terms carried.  A fold that failed leaves NaN at its points and in logp and the status 1; a slot
+// order, then the 256 partial sums by two_sum_block (gprx_loo.h).  A fold that failed leaves NaN at its points and in logp and the status 1; a slot
 // whose evaluation failed reads NaN everywhere and keeps that status.   grid = B
 // ============================================================================================
 __global__ __launch_bounds__(NTHR) void k_cv_final(DevBatch db, CvArgs a) {
-  __shared__ double ps[NTHR], pe[NTHR];
-  __shared__ int bad[NTHR];
   const int slot = blockIdx.x, tid = threadIdx.x, N = db.N;
   if (!slot_active(db, slot)) return;  // block-uniform, before the first barrier
   const size_t ro = (size_t)slot * db.Npad;
@@ -334,22 +332,10 @@ __global__ __launch_bounds__(NTHR) void k_cv_final(DevBatch db, CvArgs a) {
     two_sum_acc(s, e, a.lpf[(size_t)slot * a.F + f], 0.0);
     b |= a.fst[(size_t)slot * a.F + f];
   }
-  ps[tid] = s;
-  pe[tid] = e;
-  bad[tid] = b;
-  __syncthreads();
-  for (int h = NTHR / 2; h > 0; h >>= 1) {
-    if (tid < h) {
-      two_sum_acc(s, e, ps[tid + h], pe[tid + h]);
-      b |= bad[tid + h];
-      ps[tid] = s;
-      pe[tid] = e;
-      bad[tid] = b;
-    }
-    __syncthreads();
-  }
+  b = __syncthreads_or(b);  // any fold of the slot failed
+  const double tot = two_sum_block(s, e);
   if (tid == 0) {
-    a.logp[slot] = b ? __builtin_nan("") : s + e;
+    a.logp[slot] = b ? __builtin_nan("") : tot;
     a.st[slot] = b ? 1 : 0;
   }
 }

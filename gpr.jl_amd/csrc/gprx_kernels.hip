@@ -26,8 +26,14 @@
 #include <array>
 #include <cstdlib>
 #include <vector>
-// The parts of this translation unit, included once each and in this order (lane primitives, wave
-// MFMA cores, diagnostic stamps; further down the GEMM and the fused factorisation kernels).
+// This file is one translation unit cut along its banners.  It includes its parts once each, in this
+// order:
+//   gprx_device.h, gprx_cores.h, gprx_stamps.h                  here, before the first kernel (lane
+//                                                               primitives, wave MFMA cores, stamps)
+//   gprx_gemm.h, gprx_factor.h                                  after the Gram and single-tile kernels
+//   gprx_predcov.h, gprx_loo.h, gprx_loograd.h, gprx_cvfold.h   last, after the launchers
+// No other file includes them: they share the device globals and there is no relocatable device
+// code in this build.
 #include "gprx_device.h"
 #include "gprx_cores.h"
 #include "gprx_stamps.h"
@@ -581,7 +587,20 @@ __device__ __forceinline__ void lauum_body(const DevBatch& db) {
     lauum_unit(db, slot, jb + LU);
   }
 }
-__device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const int* ju) {
+// One gradient unit, stated once for k_lauum_grad and k_loo_grad (gprx_loograd.h): wave w forms its
+// tile m of (ti, tj) = (ju[7 + w], ju[11 + w]) with product(acc, ti, tj, ld, so), the workgroup brings
+// in the unit's point images by LDS-DMA, and the epilogue of the banner above reduces
+//   G_rc = wt_rc * W_rc * Kf_rc,   W_rc = wf(alpha_r, alpha_c, gi, gj, m_rc)   (gi, gj: global row, column)
+// to the unit's partial row part[slot][ju[0]][0 .. da + 1] = [S_p of the da active dimensions, S_f, T].
+// Only the two callables differ between the kernels; with lauum_unit's k_lauum_grad compiles to the
+// instructions it had when this text stood in lauum_unit (an epilogue cut out on its own did not: its
+// main loop waited on coarser load counts and ran 1% slower, profiles/shared_epilogue_ab.txt).
+// Every wave of the workgroup calls (the barriers are workgroup-uniform); an idle wave (ti < 0) adds
+// zeros.  Reduction order, fixed: a lane's elements in (a, b, q) order, the lanes by wave_sum /
+// row_sum16 / xor 16, 32, then the four waves' rows in order.  The diagnostic builds' marks (GTS_*,
+// GPRX_STAMPS) ride along in both kernels; their scripts launch the evaluation alone.
+template <class PF, class WF>
+__device__ __forceinline__ void grad_unit(const DevBatch& db, int slot, const int* ju, double* part, PF product, WF wf) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   // d: the active dimensions (Xc's columns, the S_p of a partial row)
   const int d = db.da, tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -590,7 +609,6 @@ __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const i
   double* sp = sm;                      // [4][SPW]
   double* als = sp + 4 * SPW;           // [nimg][64] alpha of the image points
   double* img = als + 5 * TS;           // [nimg][64][xs]
-  const int nt = db.nt;
   const double* X = db.Xc + (size_t)slot * db.Npad * xs;
   const double* al = db.alpha + (size_t)slot * db.Npad;
   const int ti = ju[7 + w], tj = ju[11 + w];
@@ -604,13 +622,7 @@ __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const i
 #endif
   [[maybe_unused]] const int gu = (ju - db.lauum_order) % (2 * LU) == 0 ? 0 : 1;  // the job's first or second unit
   GTS_L(1 + 3 * gu);
-  if (active) {  // wave-uniform: diagonal tiles form only their lower blocks
-    const double* Ap = db.Mt + so + (size_t)ti * TS * ld + ti * TS;
-    // global addressing here: the buffer-load form (k_gemm's) measured 0.15 ms slower in this kernel
-    // (11.60 / 11.66 / 11.53 against 11.41 / 11.47 / 11.44 ms, same box, bit-identical output)
-    if (ti == tj) mma_64x64_m<TRI_AB_FIRST>(acc, Ap, ld, Ap, ld, (nt - ti) * TS);
-    else mma_64x64_m<TRI_A_FIRST>(acc, Ap, ld, db.Mt + so + (size_t)ti * TS * ld + tj * TS, ld, (nt - ti) * TS);
-  }
+  if (active) product(acc, ti, tj, ld, so);  // wave-uniform
   GTS_L(2 + 3 * gu);
 #ifdef GPRX_STAMPS
   if (active && (ju - db.lauum_order) % (2 * LU) == 0) {  // the job's first (long) unit
@@ -658,7 +670,7 @@ __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const i
           const int gi = ti * TS + r, gj = tj * TS + c;
           double G = 0.0;
           if (gi < db.N && gj < db.N && gi >= gj) {
-            const double W = ar[r] * ac[c] - acc[a][b][q];
+            const double W = wf(ar[r], ac[c], gi, gj, acc[a][b][q]);
             if (gi == gj) {
               G = 0.5 * (W * sf2);
               tr += W;
@@ -747,10 +759,23 @@ __device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const i
     spw[d + 1] = tr;
   }
   __syncthreads();
-  double* out = db.grad_part + ((size_t)slot * db.ngu + ju[0]) * db.gps;
+  double* out = part + ((size_t)slot * db.ngu + ju[0]) * db.gps;
   for (int e = tid; e < d + 2; e += NTHR)
     out[e] = ((sp[e] + sp[SPW + e]) + sp[2 * SPW + e]) + sp[3 * SPW + e];
   GTS_L(3 + 3 * gu);
+}
+__device__ __forceinline__ void lauum_unit(const DevBatch& db, int slot, const int* ju) {
+  grad_unit(
+      db, slot, ju, db.grad_part,
+      [&db](d4 (&acc)[QM][QN], int ti, int tj, size_t ld, size_t so) {  // diagonal tiles form only their lower blocks
+        const int nt = db.nt;
+        const double* Ap = db.Mt + so + (size_t)ti * TS * ld + ti * TS;
+        // global addressing here: the buffer-load form (k_gemm's) measured 0.15 ms slower in this kernel
+        // (11.60 / 11.66 / 11.53 against 11.41 / 11.47 / 11.44 ms, same box, bit-identical output)
+        if (ti == tj) mma_64x64_m<TRI_AB_FIRST>(acc, Ap, ld, Ap, ld, (nt - ti) * TS);
+        else mma_64x64_m<TRI_A_FIRST>(acc, Ap, ld, db.Mt + so + (size_t)ti * TS * ld + tj * TS, ld, (nt - ti) * TS);
+      },
+      [](double alr, double alc, int, int, double m) { return alr * alc - m; });
 }
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_lauum_grad(DevBatch db) {
   lauum_body(db);
@@ -831,6 +856,42 @@ int lauum_plan(int nt, int d, int* nunits, int* nimg, int* out) {
   return nj;
 }
 
+// The unit partial rows gp[ngu][gps] of a slot (grad_unit's: S_p of the da active dimensions, S_f,
+// T) reduced into out[1 .. d + 2] = the gradient in GaussianProcesses order [log sn, log ell_1..d,
+// log sf], for k_finalize and k_loo_grad_final.  Deterministic: 4 waves x 64 lanes stride the units,
+// one parameter at a time, wave_sum, then the four waves in order.  Called by the whole workgroup in
+// workgroup-uniform control flow (two barriers a parameter).
+__device__ __forceinline__ void grad_reduce(const DevBatch& db, int slot, const double* gp, double* out) {
+  __shared__ double pr[4];
+  const int tid = threadIdx.x, d = db.d;
+  const double* P = db.params + (size_t)slot * db.pst;
+  // a partial row holds the S of the da active dimensions; a dropped (constant) dimension's
+  // distances are all 0 and so is its derivative, exactly (NaN where the distances are: P[d + 3])
+  const int da = db.da;
+  if (da < d)
+    for (int e = tid; e < d; e += NTHR) out[2 + e] = P[d + 3];  // ordered before thread 0's by the barriers below
+  int pn = 0;  // thread 0: the next dimension to look at
+  for (int q = 0; q < da + 2; ++q) {
+    double tot = 0.0;
+    for (int t = tid; t < db.ngu; t += NTHR) tot += gp[(size_t)t * db.gps + q];
+    tot = wave_sum(tot);
+    __syncthreads();
+    if ((tid & 63) == 0) pr[tid >> 6] = tot;
+    __syncthreads();
+    if (tid == 0) {
+      tot = ((pr[0] + pr[1]) + pr[2]) + pr[3];
+      int p = 0;
+      if (q < da) {  // the q-th active dimension
+        while (pn < d - 1 && !((db.amask >> pn) & 1)) ++pn;
+        p = pn < d - 1 ? pn++ : pn;
+      }
+      if (q < da) out[2 + p] = P[p] * tot;       // d / d log ell_p = il2_p * S_p
+      else if (q == da) out[2 + d] = 2.0 * tot;  // d / d log sf    = 2 S_f
+      else out[1] = P[d + 2] * tot;             // d / d log sn    = sn2 T  (T = tr(W))
+    }
+  }
+}
+
 // ============================================================================================
 // Per slot: mll = -(y.alpha + logdet + N log 2pi)/2 ; gradient (d+2) in GaussianProcesses order
 // [log sn, log ell_1..d, log sf].  grid = B
@@ -854,38 +915,7 @@ __global__ __launch_bounds__(NTHR) void k_finalize(DevBatch db, int want_grad) {
     const double log2pi = 1.8378770664093453;  // log(2pi), Julia's log2π
     out[0] = -((ya + 2.0 * ldt) + log2pi * db.N) / 2.0;
   }
-  if (want_grad) {
-    // deterministic parallel reduction over the lauum units: 4 waves x 64 lanes stride the units,
-    // one parameter at a time
-    __shared__ double pr[4];
-    const double* P = db.params + (size_t)slot * db.pst;
-    const double* gp = db.grad_part + (size_t)slot * db.ngu * db.gps;
-    // a partial row holds the S of the da active dimensions; a dropped (constant) dimension's
-    // distances are all 0 and so is its derivative, exactly (NaN where the distances are: P[d + 3])
-    const int da = db.da;
-    if (da < d)
-      for (int e = tid; e < d; e += NTHR) out[2 + e] = P[d + 3];  // ordered before thread 0's by the barriers below
-    int pn = 0;  // thread 0: the next dimension to look at
-    for (int q = 0; q < da + 2; ++q) {
-      double tot = 0.0;
-      for (int t = tid; t < db.ngu; t += NTHR) tot += gp[(size_t)t * db.gps + q];
-      tot = wave_sum(tot);
-      __syncthreads();
-      if ((tid & 63) == 0) pr[tid >> 6] = tot;
-      __syncthreads();
-      if (tid == 0) {
-        tot = ((pr[0] + pr[1]) + pr[2]) + pr[3];
-        int p = 0;
-        if (q < da) {  // the q-th active dimension
-          while (pn < d - 1 && !((db.amask >> pn) & 1)) ++pn;
-          p = pn < d - 1 ? pn++ : pn;
-        }
-        if (q < da) out[2 + p] = P[p] * tot;       // d mll / d log ell_p = il2_p * S_p
-        else if (q == da) out[2 + d] = 2.0 * tot;  // d mll / d log sf     = 2 S_f
-        else out[1] = P[d + 2] * tot;             // d mll / d log sn     = sn2 tr(W)
-      }
-    }
-  }
+  if (want_grad) grad_reduce(db, slot, db.grad_part + (size_t)slot * db.ngu * db.gps, out);
 }
 
 // ============================================================================================

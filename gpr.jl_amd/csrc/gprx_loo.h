@@ -2,12 +2,8 @@
 // (kinv = diag(K^-1) from one sweep of L^-1's lower triangle), k_loo_final (mu, var, logp_i per point
 // and logp per slot, Rasmussen & Williams 5.10-5.12), and their launchers.
 //
-// gprx_kernels.hip is one translation unit cut along its banners.  It includes, in this order:
-//   gprx_device.h, gprx_cores.h, gprx_stamps.h   (before its first kernel)
-//   gprx_gemm.h, gprx_factor.h                   (after the Gram and single-tile kernels)
-//   gprx_predcov.h, gprx_loo.h, gprx_loograd.h   (last, after the launchers)
-// No other file includes them: they share the device globals and there is no relocatable device
-// code in this build.
+// A part of gprx_kernels.hip, included there once and by no other file (the parts and their order
+// are listed at its includes).
 #pragma once
 
 namespace gprx {
@@ -114,9 +110,27 @@ __device__ __forceinline__ void two_sum_acc(double& s, double& e, double v, doub
   e += ((s - (t - bp)) + (v - bp)) + ve;
   s = t;
 }
+// The workgroup's NTHR partial sums (s, e) added by a halving tree in LDS, every addition a two-sum
+// with the error terms carried; thread 0 returns the sum, s + e of the root.  Called by the whole
+// workgroup in workgroup-uniform control flow.  (k_loo_final, k_cv_final)
+__device__ __forceinline__ double two_sum_block(double s, double e) {
+  __shared__ double ps[NTHR], pe[NTHR];
+  const int tid = threadIdx.x;
+  ps[tid] = s;
+  pe[tid] = e;
+  __syncthreads();
+  for (int h = NTHR / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      two_sum_acc(s, e, ps[tid + h], pe[tid + h]);
+      ps[tid] = s;
+      pe[tid] = e;
+    }
+    __syncthreads();
+  }
+  return s + e;
+}
 __global__ __launch_bounds__(NTHR) void k_loo_final(DevBatch db, const double* kinv, double* mu, double* var, double* lp,
                                                     double* logp) {
-  __shared__ double ps[NTHR], pe[NTHR];
   const int slot = blockIdx.x, tid = threadIdx.x, N = db.N;
   if (!slot_active(db, slot)) return;  // block-uniform, before the first barrier: the slot's rows stay as they are
   const size_t ro = (size_t)slot * db.Npad;
@@ -137,18 +151,8 @@ __global__ __launch_bounds__(NTHR) void k_loo_final(DevBatch db, const double* k
     lp[ro + i] = t;
     two_sum_acc(s, e, t, 0.0);
   }
-  ps[tid] = s;
-  pe[tid] = e;
-  __syncthreads();
-  for (int h = NTHR / 2; h > 0; h >>= 1) {
-    if (tid < h) {
-      two_sum_acc(s, e, ps[tid + h], pe[tid + h]);
-      ps[tid] = s;
-      pe[tid] = e;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) logp[slot] = s + e;
+  const double tot = two_sum_block(s, e);
+  if (tid == 0) logp[slot] = tot;
 }
 
 void launch_loo_diag(const DevBatch& b, double* kinv, hipStream_t s) {

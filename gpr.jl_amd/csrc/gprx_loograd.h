@@ -27,7 +27,8 @@
 // No atomics, no spinning; every workgroup barrier is in workgroup-uniform control flow; every
 // reduction order depends on (N, index) alone, not on B, the slot or the block that ran it.
 //
-// Included last by gprx_kernels.hip (see gprx_loo.h for the order of the parts).
+// A part of gprx_kernels.hip, included there after gprx_loo.h and by no other file (the parts and their
+// order are listed at its includes).
 #pragma once
 
 namespace gprx {
@@ -208,180 +209,26 @@ __global__ __launch_bounds__(TS) void k_loo_beta(DevBatch db, const double* bpar
 }
 
 // ============================================================================================
-// loo_grad: M's lower tiles = P_i P_j^T over K = Npad (the plain 64 x 64 core; a diagonal tile forms
-// its blocks b <= a only), one tile per wave in k_lauum_grad's units, followed by k_lauum_grad's
-// epilogue restated with
+// loo_grad: M's lower tiles = P_i P_j^T over K = Npad (mma_64x64_sq, the plain 64 x 64 core; a diagonal
+// tile forms its blocks b <= a only), one tile per wave in k_lauum_grad's units, followed by
+// k_lauum_grad's epilogue: grad_unit (gprx_kernels.hip) with this kernel's product and its W, so that
 //   G_rc = wt_rc (beta_r alpha_c + alpha_r beta_c - 2 M_rc) Kf_rc     (wt = 1/2 on the diagonal)
 // Kf from db.K as the Gram wrote it, only gi > gj read, G_rr with sf2 analytically, row and column
-// sums and Q = G Xc on the MFMA pipe as lauum_unit forms them, the da active dimensions only, the
-// trace kept for sn.  lauum_unit's epilogue is restated here rather than shared: k_lauum_grad is left
-// exactly as it was.  LDS: lauum_unit's layout and size (beta comes from global memory), so two
-// workgroups fit a CU wherever k_lauum_grad's do.  One partial row per unit: gpart[slot][unit][gps].
+// sums and Q = G Xc on the MFMA pipe, the da active dimensions only, the trace kept for sn.
+// LDS: lauum_unit's layout and size (beta comes from global memory), so two workgroups fit a CU
+// wherever k_lauum_grad's do.  One partial row per unit: gpart[slot][unit][gps].
 // grid = grid_blocks(B, nlj)
 // ============================================================================================
-template <bool SAME>
-__device__ __forceinline__ void mma_64x64_sq(d4 (&acc)[QM][QN], const double* __restrict__ A, size_t lda,
-                                             const double* __restrict__ B, size_t ldb, int K) {
-  constexpr int MODE = SAME ? TRI_AB_FIRST : PLAIN;  // trip 4: the dense masks (SAME: B = A, blocks b <= a)
-  const int nst = __builtin_amdgcn_readfirstlane(K / (4 * Q4SD));  // even: K is whole 64-tiles
-  if (nst <= 0) return;
-  const CorePtrG pa = core_ptr_g(A, lda), pb = core_ptr_g(B, ldb);
-  Frag4 f0, f1;
-  core_load<MODE, 4>(f0, pa, pb, 0);
-  for (int it = 0; it < nst; it += 2) {
-    __builtin_amdgcn_sched_barrier(0);
-    core_load<MODE, 4>(f1, pa, pb, it + 1);
-    core_mma<MODE, 4>(acc, f0);
-    core_groups<MODE>();
-    __builtin_amdgcn_sched_barrier(0);
-    const int n2 = (it + 2 < nst) ? it + 2 : nst - 1;
-    core_load<MODE, 4>(f0, pa, pb, n2);
-    core_mma<MODE, 4>(acc, f1);
-    core_groups<MODE>();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
 __device__ __forceinline__ void loo_grad_unit(const DevBatch& db, int slot, const int* ju, const double* beta, double* gpart) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int d = db.da, tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int xs = db.xs, xt = TS * xs;  // point-tile image: [64][xs]
-  const int nimg = ju[1];
-  double* sp = sm;             // [4][SPW]
-  double* als = sp + 4 * SPW;  // [nimg][64] alpha of the image points
-  double* img = als + 5 * TS;  // [nimg][64][xs]
-  const double* X = db.Xc + (size_t)slot * db.Npad * xs;
-  const double* al = db.alpha + (size_t)slot * db.Npad;
   const double* be = beta + (size_t)slot * db.Npad;
-  const int ti = ju[7 + w], tj = ju[11 + w];
-  const bool active = ti >= 0;
-  const int l = tid & 63, lr = l & 15, lk = l >> 4;
-  d4 acc[QM][QN];
-  acc4_zero(acc);
-  const size_t ld = db.ld, so = (size_t)slot * db.mat;
-  if (active) {  // wave-uniform
-    const double* Pi = db.Lw + so + ti * TS;
-    if (ti == tj) mma_64x64_sq<true>(acc, Pi, ld, Pi, ld, db.Npad);
-    else mma_64x64_sq<false>(acc, Pi, ld, db.Lw + so + tj * TS, ld, db.Npad);
-  }
-  for (int i = 0; i < nimg; ++i) dma_tile(img + i * xt, X + (size_t)ju[2 + i] * xt, xt);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA landed
-  __syncthreads();                                   // ... and every other wave's
-  double sf = 0.0, tr = 0.0;
-  double* spw = sp + w * SPW;
-  for (int e = l; e < SPW; e += 64) spw[e] = 0.0;
-  const double* P = db.params + (size_t)slot * db.pst;
-  for (int e = tid; e < nimg * TS; e += NTHR) als[e] = al[ju[2 + (e >> 6)] * TS + (e & 63)];
-  __syncthreads();
-  if (active) {
-    const double sf2 = P[db.d];
-    const int ir = ju[15 + w], ic = ju[19 + w];
-    const double* xr = img + ir * xt;  // [r][xs]
-    const double* xc = img + ic * xt;  // [c][xs]
-    const double* ar = als + ir * TS;
-    const double* ac = als + ic * TS;
-    const double* Kf = db.K + so + (size_t)(tj * TS) * ld + ti * TS;
-    const size_t ldk = ld;
-#pragma unroll
-    for (int a = 0; a < QM; ++a) {
-      double kf[QN][4];
-#pragma unroll
-      for (int b = 0; b < QN; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kf[b][q] = Kf[(size_t)(16 * b + lk + 4 * q) * ldk + 16 * a + lr];
-      const double brv = be[ti * TS + 16 * a + lr], arv = ar[16 * a + lr];
-#pragma unroll
-      for (int b = 0; b < QN; ++b) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int r = 16 * a + lr, c = 16 * b + lk + 4 * q;
-          const int gi = ti * TS + r, gj = tj * TS + c;
-          double G = 0.0;
-          if (gi < db.N && gj < db.N && gi >= gj) {
-            const double W = (brv * ac[c] + arv * be[gj]) - 2.0 * acc[a][b][q];
-            if (gi == gj) {
-              G = 0.5 * (W * sf2);
-              tr += W;
-            } else {
-              G = W * kf[b][q];
-            }
-            sf += G;
-          }
-          acc[a][b][q] = G;
-        }
-      }
-    }
-    double R[QM], Cs[QN][4];
-#pragma unroll
-    for (int a = 0; a < QM; ++a) {
-      double s = 0.0;
-#pragma unroll
-      for (int b = 0; b < QN; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s += acc[a][b][q];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      R[a] = s;
-    }
-#pragma unroll
-    for (int b = 0; b < QN; ++b)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        Cs[b][q] = row_sum16((acc[0][b][q] + acc[1][b][q]) + (acc[2][b][q] + acc[3][b][q]));
-      }
-    const int H = (d + 15) >> 4;
-#pragma unroll 1
-    for (int h = 0; h < H; ++h) {
-      const int pA = 16 * h + lr, pAc = pA < d ? pA : d - 1;
-      double xa[QN][4];
-      double t2 = 0.0;
-#pragma unroll
-      for (int b = 0; b < QN; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          xa[b][q] = xc[(16 * b + 4 * q + lk) * xs + pAc];
-          t2 = fma(xa[b][q] * xa[b][q], Cs[b][q], t2);
-        }
-      double t13[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int a = 0; a < QM; ++a) {
-        d4 Q = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int b = 0; b < QN; ++b)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) Q = mfma(xa[b][q], acc[a][b][q], Q);
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          const int p = 16 * h + lk + 4 * qq;
-          const double x = xr[(16 * a + lr) * xs + (p < d ? p : d - 1)];
-          t13[qq] = fma(x, fma(x, R[a], -2.0 * Q[qq]), t13[qq]);
-        }
-      }
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) t13[qq] = row_sum16(t13[qq]);
-      t2 += __shfl_xor(t2, 16);
-      t2 += __shfl_xor(t2, 32);
-      if (lr == 0) {
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          const int p = 16 * h + lk + 4 * qq;
-          if (p < d) spw[p] = t13[qq];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (lk == 0 && pA < d) spw[pA] += t2;
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-  sf = wave_sum(sf);
-  tr = wave_sum(tr);
-  if (l == 0) {
-    spw[d] = sf;
-    spw[d + 1] = tr;
-  }
-  __syncthreads();
-  double* out = gpart + ((size_t)slot * db.ngu + ju[0]) * db.gps;
-  for (int e = tid; e < d + 2; e += NTHR) out[e] = ((sp[e] + sp[SPW + e]) + sp[2 * SPW + e]) + sp[3 * SPW + e];
+  grad_unit(
+      db, slot, ju, gpart,
+      [&db](d4 (&acc)[QM][QN], int ti, int tj, size_t ld, size_t so) {
+        const double* Pi = db.Lw + so + ti * TS;
+        if (ti == tj) mma_64x64_sq<true>(acc, Pi, ld, Pi, ld, db.Npad);
+        else mma_64x64_sq<false>(acc, Pi, ld, db.Lw + so + tj * TS, ld, db.Npad);
+      },
+      [be](double alr, double alc, int gi, int gj, double m) { return (be[gi] * alc + alr * be[gj]) - 2.0 * m; });
 }
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_loo_grad(DevBatch db, const double* beta,
                                                                                               double* gpart) {
@@ -398,13 +245,12 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 
 // ============================================================================================
 // loo_grad_final: out[slot] = [logp, d logp / d (log sn, log ell_1..d, log sf)], the unit partials
-// reduced as k_finalize reduces the marginal likelihood's (threads stride the units, wave_sum, the four
-// waves in order) and by its formulas: il2_p S_p, 2 S_f, sn2 tr(W_loo).  An inactive (constant)
+// reduced by grad_reduce (gprx_kernels.hip), as k_finalize reduces the marginal likelihood's (threads
+// stride the units, wave_sum, the four waves in order): il2_p S_p, 2 S_f, sn2 tr(W_loo).  An inactive (constant)
 // dimension gets exactly 0 (NaN where its distances are: params[d + 3]).  logp is k_loo_final's, copied.
 // A slot whose last evaluation did not end with status 0 gets NaN throughout.   grid = B
 // ============================================================================================
 __global__ __launch_bounds__(NTHR) void k_loo_grad_final(DevBatch db, const double* gpart, const double* logp, double* out_all) {
-  __shared__ double pr[4];
   const int slot = blockIdx.x, tid = threadIdx.x, d = db.d;
   if (!slot_active(db, slot)) return;  // block-uniform, before the first barrier: the slot's row stays as it is
   double* out = out_all + (size_t)slot * (d + 3);
@@ -413,31 +259,7 @@ __global__ __launch_bounds__(NTHR) void k_loo_grad_final(DevBatch db, const doub
     return;
   }
   if (tid == 0) out[0] = logp[slot];
-  const double* P = db.params + (size_t)slot * db.pst;
-  const double* gp = gpart + (size_t)slot * db.ngu * db.gps;
-  const int da = db.da;
-  if (da < d)
-    for (int e = tid; e < d; e += NTHR) out[2 + e] = P[d + 3];  // ordered before thread 0's by the barriers below
-  int pn = 0;  // thread 0: the next dimension to look at
-  for (int q = 0; q < da + 2; ++q) {
-    double tot = 0.0;
-    for (int t = tid; t < db.ngu; t += NTHR) tot += gp[(size_t)t * db.gps + q];
-    tot = wave_sum(tot);
-    __syncthreads();
-    if ((tid & 63) == 0) pr[tid >> 6] = tot;
-    __syncthreads();
-    if (tid == 0) {
-      tot = ((pr[0] + pr[1]) + pr[2]) + pr[3];
-      int p = 0;
-      if (q < da) {  // the q-th active dimension
-        while (pn < d - 1 && !((db.amask >> pn) & 1)) ++pn;
-        p = pn < d - 1 ? pn++ : pn;
-      }
-      if (q < da) out[2 + p] = P[p] * tot;       // d logp / d log ell_p = il2_p S_p
-      else if (q == da) out[2 + d] = 2.0 * tot;  // d logp / d log sf    = 2 S_f
-      else out[1] = P[d + 2] * tot;             // d logp / d log sn    = sn2 tr(W_loo)
-    }
-  }
+  grad_reduce(db, slot, gpart + (size_t)slot * db.ngu * db.gps, out);
 }
 
 static void set_loograd_attributes() {

@@ -2,12 +2,8 @@
 // K*^T L^-T stored), k_pred_cov (Sigma = K** - V^T V, lower tiles and their mirrors), k_cov_chol
 // (lower Cholesky of Sigma with the jitter ladder) and k_cov_sample (mu + L z), and their launchers.
 //
-// gprx_kernels.hip is one translation unit cut along its banners.  It includes, in this order:
-//   gprx_device.h, gprx_cores.h, gprx_stamps.h   (before its first kernel)
-//   gprx_gemm.h, gprx_factor.h                   (after the Gram and single-tile kernels)
-//   gprx_predcov.h, gprx_loo.h, gprx_loograd.h   (last, after the launchers)
-// No other file includes them: they share the device globals and there is no relocatable device
-// code in this build.
+// A part of gprx_kernels.hip, included there once and by no other file (the parts and their order
+// are listed at its includes).
 #pragma once
 
 namespace gprx {
